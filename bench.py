@@ -38,6 +38,12 @@ after the other and reports their times: the load balance an R-GPU run would see
 --workload c4 (BASELINE.json config 4): Terrain.shadow over 144 diurnal sun positions of the c3 tile, outputs resident
 in HBM; a step = one pass over all sun positions; its own roofline (shadow kernel).
 
+`--dump-outputs DIR` (c3 without row sharding): after the timed steps, what the last of them computed goes to
+DIR/<name>.npy -- svf.npy (its rows), hori_sample.npy (the horizon at a fixed, seeded sample of its cells) and
+hori_sample_cells.npy (their row and column); the inputs are seeded, so two builds can be compared file for file.
+The flag is refused for c4, c5 and the row-sharded c3 line (`--gpus N` with N > 1, HZ_FORCE_DIST): those runs cannot be
+compared output for output this way (their SVF can be saved with --dump-svf-rows / --dump-path).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -104,6 +110,9 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-count", action="store_true", help="skip the counter pass (roofline is I/O only)")
     ap.add_argument("--no-peaks", action="store_true", help="skip the machine calibration kernels")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="c3: after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64: the SVF of "
+                         "its rows, the horizon at a fixed, seeded sample of its cells; at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -203,7 +212,9 @@ def self_launch(args):
     import subprocess
     import torch
     backend = os.environ.get("HZ_DIST_BACKEND", "nccl")
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    # device_count() asks amd-smi when it can, without starting the HIP runtime (is_available() would start it): the launcher
+    # itself then holds no GPU context next to its N ranks
+    have = max(torch.cuda.device_count(), 0)
     if have < 1:
         raise SystemExit("bench.py needs an MI355X (no HIP device visible)")
     if have < args.gpus and backend != "gloo":
@@ -223,6 +234,13 @@ def self_launch(args):
 
 def main():
     args = parse()
+    if args.dump_outputs:
+        sharded = args.scaling != "weak" and (max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1
+                                              or bool(os.environ.get("HZ_FORCE_DIST")))
+        if args.workload != "c3" or sharded:
+            raise SystemExit("bench.py --dump-outputs: implemented for the c3 line without row sharding (one rank, or --scaling weak)")
+        if args.steps is not None and args.steps < 1:
+            raise SystemExit("bench.py --dump-outputs: needs at least one timed step")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -343,6 +361,49 @@ def make_scene(ctx, g, n):
     return scene, scene_stats, t_build, t_bcast
 
 
+DUMP_SVF_BYTES = 52 << 20     # --dump-outputs: the SVF of the last step's rows whole up to this size (3569^2 cells: 51 MB) ...
+DUMP_HORI_BYTES = 8 << 20     # ... and the horizon of a sample of its cells: < 64 MB in all
+
+
+def sample_cells(rows, cols, k, seed):
+    """k distinct flat indices into a rows x cols grid (all of them when k >= rows x cols), ascending: a fixed, seeded
+    choice, so that two runs with the same arguments sample the same cells."""
+    n = rows * cols
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_step_outputs(path, d_hori, d_svf, rb, re):
+    """--dump-outputs: what the caller of the timed path received from its last step, which covered inner-domain rows
+    [rb, re): the SVF of those rows (d_svf rows rb..re-1) and their horizon (d_hori, slab-local, rows x in1 x A).  The SVF is
+    written whole when it fits DUMP_SVF_BYTES, else at a seeded sample of cells; the horizon at a seeded sample of cells
+    (all azimuths of each).  *_cells files hold the (inner-domain row, column) of every sampled cell.  Returns
+    {name: shape} of the files written."""
+    import torch
+    rows, in1, A = re - rb, d_svf.shape[1], d_hori.shape[2]
+    os.makedirs(path, exist_ok=True)
+
+    def take(flat, idx):
+        return flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+
+    def cells(idx):
+        return np.stack([idx // in1 + rb, idx % in1], axis=1).astype(np.float64)
+
+    files = {}
+    svf = d_svf[rb:re].reshape(-1)
+    if svf.numel() * 4 <= DUMP_SVF_BYTES:
+        files["svf"] = svf.cpu().numpy().reshape(rows, in1)
+    else:
+        idx = sample_cells(rows, in1, DUMP_SVF_BYTES // (4 + 16), seed=20261015)
+        files["svf_sample"], files["svf_sample_cells"] = take(svf, idx), cells(idx)
+    idx = sample_cells(rows, in1, DUMP_HORI_BYTES // (4 * A + 16), seed=20261016)
+    files["hori_sample"], files["hori_sample_cells"] = take(d_hori[:rows].reshape(rows * in1, A), idx), cells(idx)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in files.items()}
+
+
 def barrier(ctx):
     import torch
     import torch.distributed as dist
@@ -444,6 +505,7 @@ def run_c3(ctx):
         imbalance = 1.0
     if rank != 0:
         return None
+    dumped = dump_step_outputs(args.dump_outputs, d_hori, d_svf, rb, re) if args.dump_outputs else None
 
     k_launch_s = stats.t_kernel_s / max(steps, 1)        # HIP events on the kernel's stream
     rays_launch = stats.num_rays / max(steps, 1)
@@ -491,6 +553,8 @@ def run_c3(ctx):
                 tj.get("rocm"), tj.get("device"), out["config"]["rocm"], out["config"]["device"])
     except Exception:
         pass
+    if dumped is not None:
+        out["config"]["dump_outputs"] = dumped
     if args.dump_path and args.dump_svf_rows == "all" and n_slabs == 1:
         np.save(args.dump_path, d_svf.cpu().numpy())
     if world == 1 and not args.no_extras and n_slabs == 1:

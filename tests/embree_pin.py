@@ -9,8 +9,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 HORIZON = os.path.join(HERE, "golden", "embree_horizon.npz")
 SHADOW = os.path.join(HERE, "golden", "embree_shadow.npz")
-MISSING = ("tests/golden/embree_*.npz not present: the ray-casting decisions stay UNPINNED against the Embree reference -- "
-           "run scripts/make_embree_fixtures.py in an environment with the reference installed (DESIGN.md section 3)")
+MISSING = ("needs the outputs of the reference, which needs the Intel Embree 4 and oneTBB libraries: tests/golden/embree_*.npz "
+           "not present, the ray-casting decisions stay UNPINNED against the Embree reference -- run "
+           "scripts/make_embree_fixtures.py in an environment with the reference installed (DESIGN.md section 3)")
 
 
 def _harness():

@@ -105,9 +105,20 @@ def test_plain_bench_gpus_2_starts_two_ranks_and_shards_the_tile(tmp_path):
         assert len(pr[key]["slab_ms"]) == n_r and 0.1 < pr[key]["predicted_efficiency"] <= 1.25
 
 
+def _gpus_visible():
+    import torch
+    return torch.cuda.device_count() if torch.cuda.is_available() else 0
+
+
 def test_plain_bench_gpus_8_world_of_eight_on_one_gpu(tmp_path):
-    """The world size the driver's scaling run ends with: `python bench.py --gpus 8` (eight ranks sharing the one GPU over
-    gloo) -- eight disjoint slabs that cover the tile, every rank's time reported, the gathered SVF equal to the N = 1 SVF."""
+    """The world size the driver's scaling run ends with: `python bench.py --gpus 8` (eight ranks over gloo) -- eight
+    disjoint slabs that cover the tile, every rank's time reported, the gathered SVF equal to the N = 1 SVF.  Runs where
+    every rank has a GPU of its own: eight ranks on ONE device, with this process beside them, hold nine or more HIP
+    contexts on it at once, more than a node shared with other jobs lets one device carry.  On one GPU,
+    test_plain_bench_gpus_4_world_of_four_on_one_gpu runs these checks, and the config-5 job over the same ranks, for four."""
+    have = _gpus_visible()
+    if have < 8:
+        pytest.skip("needs 8 GPUs (one per rank), found %d" % have)
     np = pytest.importorskip("numpy")
     p, dump8 = _plain(tmp_path, "eight", "--no-count", "--no-peaks", gpus=8)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -121,6 +132,38 @@ def test_plain_bench_gpus_8_world_of_eight_on_one_gpu(tmp_path):
     r, dump1 = _plain(tmp_path, "one", "--no-count", "--no-peaks", "--no-extras", gpus=1)
     assert r.returncode == 0, r.stderr[-3000:]
     assert np.array_equal(np.load(dump8), np.load(dump1))
+
+
+def test_plain_bench_gpus_4_world_of_four_on_one_gpu(tmp_path):
+    """A world of four ranks on the one GPU of the test box (gloo): four disjoint slabs of 142 - 143 rows that cover the
+    tile, every rank's time reported, the gathered SVF equal to the N = 1 SVF; then the config-5 job over the same four
+    ranks (extras.c5, an 801^2 mosaic): four slabs that cover its 769 inner rows and a gathered SVF equal to one rank's."""
+    np = pytest.importorskip("numpy")
+    dump_c5 = str(tmp_path / "c5_four.npy")
+    p, dump4 = _plain(tmp_path, "four", "--no-count", "--no-peaks", "--c5-tile", "801", "--dump-c5-path", dump_c5, gpus=4)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    c = d["config"]
+    sl = c["slabs"]
+    assert d["n_gpus"] == 4 and d["scaling"] == "strong" and len(sl) == 4 and len(c["t_ranks_s"]) == 4
+    assert sl[0][0] == 0 and sl[-1][1] == 569 and all(sl[i][1] == sl[i + 1][0] for i in range(3))
+    assert all(142 <= b - a <= 143 for a, b in sl) and c["gathered_svf_finite"] is True
+    assert c["cells_per_step"] == 569 * 569 and c["load_imbalance_max_over_mean"] >= 1.0
+    e5 = d["extras"]["c5"]
+    s5 = e5["slabs"]
+    assert e5["n_gpus"] == 4 and len(s5) == 4 and len(e5["t_ranks_s"]) == 4 and e5["gathered_svf_finite"] is True
+    assert s5[0][0] == 0 and s5[-1][1] == 769 and all(s5[i][1] == s5[i + 1][0] for i in range(3))
+    assert "801x801" in e5["workload"]
+    r, dump1 = _plain(tmp_path, "one", "--no-count", "--no-peaks", "--no-extras", gpus=1)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert np.array_equal(np.load(dump4), np.load(dump1))
+    env5 = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29629")
+    dump_c5_one = str(tmp_path / "c5_one.npy")
+    q5 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--tile", "801", "--azim", "72",
+                         "--dump-svf-rows", "all", "--dump-path", dump_c5_one], cwd=ROOT, env=env5, capture_output=True, text=True, timeout=600)
+    assert q5.returncode == 0, q5.stderr[-3000:]
+    a5, b5 = np.load(dump_c5), np.load(dump_c5_one)
+    assert a5.shape == (769, 769) and np.isfinite(a5).all() and np.array_equal(a5, b5)
 
 
 def test_plain_bench_gpus_2_broadcasting_vertices_only(tmp_path):
