@@ -52,13 +52,22 @@ class hz_stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class hz_topo_out(C.Structure):
+    """Maps of the further horizon reductions (hz_horizon_gridded_ex / _scene_ex); `size` is set to sizeof(hz_topo_out)."""
+    _fields_ = [("size", C.c_int32), ("vsf", C.c_void_p), ("openness", C.c_void_p)]
+
+    def __init__(self, vsf=None, openness=None):
+        super().__init__(C.sizeof(hz_topo_out), vsf, openness)
+
+
 # every symbol include/horayzon_hip.h declares (tests check that all are exported)
 SYMBOLS = (
     "hz_last_error", "hz_abi_struct_sizes", "hz_abi_version", "hz_device_count", "hz_device_info",
     "hz_scene_create", "hz_scene_blob", "hz_scene_vertices", "hz_scene_adopt", "hz_scene_destroy",
-    "hz_horizon_gridded", "hz_horizon_gridded_scene", "hz_horizon_locations",
+    "hz_horizon_gridded", "hz_horizon_gridded_scene", "hz_horizon_gridded_ex", "hz_horizon_gridded_scene_ex",
+    "hz_horizon_locations",
     "hz_horizon_locations_scene", "hz_horizon_tables",
-    "hz_sky_view_factor", "hz_visible_sky_fraction", "hz_topographic_openness",
+    "hz_sky_view_factor", "hz_visible_sky_fraction", "hz_topographic_openness", "hz_topo_params",
     "hz_slope_plane_meth", "hz_slope_vector_meth", "hz_lonlat2ecef", "hz_ecef2enu", "hz_wgs2swiss", "hz_swiss2wgs",
     "hz_ecef2enu_vector", "hz_surf_norm", "hz_north_dir", "hz_vert_grid_len", "hz_pack_vertices",
     "hz_debug_sort_pairs", "hz_debug_exclusive_scan",
@@ -120,6 +129,9 @@ def lib():
     L.hz_horizon_gridded_scene.argtypes = [
         vp, vp, vp, ip, ip, vp, ip, ip, ip, C.c_float, C.c_float, C.c_char_p,
         C.c_float, vp, C.c_float, C.c_float, C.POINTER(hz_opts), C.POINTER(hz_stats)]
+    L.hz_horizon_gridded_ex.argtypes = L.hz_horizon_gridded.argtypes[:-1] + [C.POINTER(hz_topo_out), C.POINTER(hz_stats)]
+    L.hz_horizon_gridded_scene_ex.argtypes = L.hz_horizon_gridded_scene.argtypes[:-1] + [C.POINTER(hz_topo_out),
+                                                                                         C.POINTER(hz_stats)]
     L.hz_horizon_locations.argtypes = [
         vp, ip, ip, vp, vp, vp, vp, vp, ip, ip, C.c_float, C.c_float, C.c_char_p, C.c_char_p,
         C.c_float, vp, ip, C.POINTER(hz_opts), C.POINTER(hz_stats)]
@@ -131,6 +143,7 @@ def lib():
     L.hz_sky_view_factor.argtypes = [vp, vp, vp, ip, ip, ip, vp, ip]
     L.hz_visible_sky_fraction.argtypes = [vp, vp, vp, ip, ip, ip, vp, ip]
     L.hz_topographic_openness.argtypes = [vp, vp, ip, ip, ip, vp, ip]
+    L.hz_topo_params.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp, vp, ip]
     L.hz_slope_plane_meth.argtypes = [vp, vp, vp, ip, ip, vp, ip, vp, ip]
     L.hz_slope_vector_meth.argtypes = [vp, vp, vp, ip, ip, vp, ip, vp, ip]
     L.hz_lonlat2ecef.argtypes = [vp, vp, vp, C.c_size_t, ip, vp, vp, vp, ip]

@@ -547,7 +547,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
                        int offset_1, float *hori_buffer, int dim_in_0, int dim_in_1, int azim_num,
                        float dist_search, float hori_acc, const char *ray_algorithm,
                        float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
-                       const hz_opts *opts, hz_stats *stats) {
+                       const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
     int alg = 2;
     int rc = parse_alg(ray_algorithm, &alg);
     if (rc) return rc;
@@ -561,6 +561,12 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     if (opts && opts->svf && !opts->vec_tilt) return set_error(HZ_ERR_ARG, "opts.svf needs opts.vec_tilt");
     // the SVF weights sectors by azim[1] - azim[0] (topo_param.pyx:433): undefined for a single azimuth
     if (opts && opts->svf && azim_num < 2) return set_error(HZ_ERR_ARG, "opts.svf needs azim_num >= 2");
+    // further reductions (hz_topo_out): the VSF as the SVF (tilt, azim[1] - azim[0], :520); openness needs neither
+    if (topo && topo->size != (int32_t)sizeof(hz_topo_out))
+        return set_error(HZ_ERR_ARG, "topo.size is %d, expected sizeof(hz_topo_out) = %d", topo->size, (int)sizeof(hz_topo_out));
+    const bool want_vsf = topo && topo->vsf, want_open = topo && topo->openness;
+    if (want_vsf && !(opts && opts->vec_tilt)) return set_error(HZ_ERR_ARG, "topo.vsf needs opts.vec_tilt");
+    if (want_vsf && azim_num < 2) return set_error(HZ_ERR_ARG, "topo.vsf needs azim_num >= 2");
     // row slab (include/horayzon_hip.h): {0, 0} = the whole inner domain (a zeroed struct), row_end == -1 = dim_in_0,
     // anything else must satisfy 0 <= row_begin <= row_end <= dim_in_0; begin == end is an empty slab: nothing to do
     int row_begin = 0, row_end = dim_in_0;
@@ -600,7 +606,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     if ((rc = d_norm.bind(vec_norm + 3 * src_off, slab_cells * 3, st))) return rc;
     if ((rc = d_north.bind(vec_north + 3 * src_off, slab_cells * 3, st))) return rc;
     if ((rc = d_mask.bind(mask + src_off, slab_cells, st))) return rc;
-    if (opts && opts->svf) if ((rc = d_tilt.bind(opts->vec_tilt + 3 * src_off, slab_cells * 3, st))) return rc;
+    if ((opts && opts->svf) || want_vsf) if ((rc = d_tilt.bind(opts->vec_tilt + 3 * src_off, slab_cells * 3, st))) return rc;
     const float *norm0 = d_norm.dev - 3 * in_off, *north0 = d_north.dev - 3 * in_off;
     const uint8_t *mask0 = d_mask.dev - in_off;
     const float *tilt0 = d_tilt.dev ? d_tilt.dev - 3 * in_off : nullptr;
@@ -610,9 +616,10 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     if ((rc = d_es.bind(tb.elev_sin.data(), (size_t)tb.elev_num, st))) return rc;
     if ((rc = d_ec.bind(tb.elev_cos.data(), (size_t)tb.elev_num, st))) return rc;
     if ((rc = d_mid.bind(tb.mid_idx.data(), tb.mid_idx.size(), st))) return rc;
-    DevOut<float> d_hori, d_svf;
+    DevOut<float> d_hori, d_svf, d_vsf, d_open;
     DevIn<float> d_azim;
     const bool want_svf = opts && opts->svf;
+    const bool want_topo = want_svf || want_vsf || want_open;
     // hori_buffer addresses inner-domain row 0 (the reference's layout) unless opts.hori_is_slab says it addresses
     // row_begin.  Only the slab itself is ever classified or written: `hori_row0` is an address used for
     // arithmetic alone (it may lie below the caller's allocation when a resident slab buffer is passed).
@@ -621,6 +628,11 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     float *hori_row0 = hori_slab_host ? hori_slab_host - (size_t)row_begin * dim_in_1 * azim_num : nullptr;
     float *svf_slab = want_svf ? (hori_is_slab ? opts->svf : opts->svf + (size_t)row_begin * dim_in_1) : nullptr;
     if ((rc = d_svf.bind(svf_slab, svf_slab ? slab_cells : 0))) return rc;
+    // the maps of hz_topo_out address row 0 or row_begin exactly as opts.svf does
+    float *vsf_slab = want_vsf ? (hori_is_slab ? topo->vsf : topo->vsf + (size_t)row_begin * dim_in_1) : nullptr;
+    float *open_slab = want_open ? (hori_is_slab ? topo->openness : topo->openness + (size_t)row_begin * dim_in_1) : nullptr;
+    if ((rc = d_vsf.bind(vsf_slab, vsf_slab ? slab_cells : 0))) return rc;
+    if ((rc = d_open.bind(open_slab, open_slab ? slab_cells : 0))) return rc;
     // rows per launch: the whole slab when `hori` is device memory.  Otherwise the horizon of a chunk
     // of rows lives in a bounded temporary: one <= 4 GiB buffer when only the SVF is wanted, two of
     // them when `hori` is host memory -- chunk c is copied out on a second stream while chunk c + 1 is
@@ -632,7 +644,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     const size_t row_bytes = (size_t)dim_in_1 * azim_num * 4;
     const bool stream_out = !skip_hori && !is_device_ptr(hori_slab_host);
     if (skip_hori || stream_out) {
-        if (skip_hori && !want_svf) return set_error(HZ_ERR_ARG, "skip_hori without svf: nothing to compute");
+        if (skip_hori && !want_topo) return set_error(HZ_ERR_ARG, "skip_hori without svf, vsf or openness: nothing to compute");
         if ((rc = alloc_hori_chunk(row_end - row_begin, row_bytes, skip_hori, (opts && opts->chunk_rows > 0) ? opts->chunk_rows : 0, &chunk_rows, &tmp_hori)))
             return rc;
         tmp_bytes = (size_t)chunk_rows * row_bytes;
@@ -641,7 +653,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
         if ((rc = d_hori.bind(hori_slab_host, slab_cells * (size_t)azim_num))) return rc;
     }
     std::vector<float> azim_h;
-    if (want_svf) {   // azim as the wrapper recomputes it, horizon.pyx:191-195
+    if (want_topo) {   // azim as the wrapper recomputes it, horizon.pyx:191-195
         azim_h.resize((size_t)azim_num);
         for (int i = 0; i < azim_num; i++) azim_h[(size_t)i] = (float)(((2 * M_PI) / azim_num) * i);
         if ((rc = d_azim.bind(azim_h.data(), (size_t)azim_num, st))) return rc;
@@ -872,9 +884,17 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
             }
             if (!rc && mon.active) rc = mon.collect(st, &n_verified, &n_mon_violations);
             (void)hipEventRecord(e.b, st);
-            if (!rc && want_svf)
-                rc = svf_launch(d_azim.dev, hori_chunk, tilt0 + 3 * (size_t)rb * dim_in_1, re - rb, dim_in_1,
-                                azim_num, d_svf.dev + (size_t)(rb - row_begin) * dim_in_1, st);
+            if (!rc && want_topo) {
+                // one reduction launch per chunk: k_topo<0> itself when the SVF is the only map, the fused kernel otherwise
+                const size_t o = (size_t)(rb - row_begin) * dim_in_1;
+                const float *tilt_chunk = tilt0 ? tilt0 + 3 * (size_t)rb * dim_in_1 : nullptr;
+                if (!want_vsf && !want_open)
+                    rc = svf_launch(d_azim.dev, hori_chunk, tilt_chunk, re - rb, dim_in_1, azim_num, d_svf.dev + o, st);
+                else
+                    rc = topo_multi_launch(d_azim.dev, hori_chunk, tilt_chunk, re - rb, dim_in_1, azim_num,
+                                           want_svf ? d_svf.dev + o : nullptr, want_vsf ? d_vsf.dev + o : nullptr,
+                                           want_open ? d_open.dev + o : nullptr, st);
+            }
             (void)hipEventRecord(e.c, st);
             if (!rc && stream_out && n_chunk >= 1) rc = copy_out(n_chunk - 1);
             if (rc) return fail(rc);
@@ -910,6 +930,8 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     HZ_HIP(hipGetLastError());
     if ((rc = d_hori.finish(st))) return rc;
     if ((rc = d_svf.finish(st))) return rc;
+    if ((rc = d_vsf.finish(st))) return rc;
+    if ((rc = d_open.finish(st))) return rc;
     HZ_HIP(hipStreamSynchronize(st));
     const double d2h_s = t_d2h.stop();
 
@@ -1115,15 +1137,25 @@ int hz_scene_destroy(hz_scene *scene) {
     return HZ_OK;
 }
 
+int hz_horizon_gridded_scene_ex(const hz_scene *scene, const float *vec_norm, const float *vec_north,
+                                int offset_0, int offset_1, float *hori_buffer, int dim_in_0, int dim_in_1,
+                                int azim_num, float dist_search, float hori_acc, const char *ray_algorithm,
+                                float elev_ang_low_lim, const uint8_t *mask, float hori_fill,
+                                float ray_org_elev, const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    if (!scene) return set_error(HZ_ERR_ARG, "scene is NULL");
+    return horizon_run(reinterpret_cast<const Scene *>(scene), vec_norm, vec_north, offset_0, offset_1,
+                       hori_buffer, dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                       elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, stats);
+}
+
 int hz_horizon_gridded_scene(const hz_scene *scene, const float *vec_norm, const float *vec_north,
                              int offset_0, int offset_1, float *hori_buffer, int dim_in_0, int dim_in_1,
                              int azim_num, float dist_search, float hori_acc, const char *ray_algorithm,
                              float elev_ang_low_lim, const uint8_t *mask, float hori_fill,
                              float ray_org_elev, const hz_opts *opts, hz_stats *stats) {
-    if (!scene) return set_error(HZ_ERR_ARG, "scene is NULL");
-    return horizon_run(reinterpret_cast<const Scene *>(scene), vec_norm, vec_north, offset_0, offset_1,
-                       hori_buffer, dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
-                       elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, stats);
+    return hz_horizon_gridded_scene_ex(scene, vec_norm, vec_north, offset_0, offset_1, hori_buffer, dim_in_0, dim_in_1,
+                                       azim_num, dist_search, hori_acc, ray_algorithm, elev_ang_low_lim, mask, hori_fill,
+                                       ray_org_elev, opts, nullptr, stats);
 }
 
 int hz_horizon_gridded(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
@@ -1133,6 +1165,19 @@ int hz_horizon_gridded(const float *vert_grid, int dem_dim_0, int dem_dim_1, con
                        int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
                        float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
                        const hz_opts *opts, hz_stats *stats) {
+    return hz_horizon_gridded_ex(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north, offset_0, offset_1, hori_buffer,
+                                 dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm, geom_type, vert_simp,
+                                 num_vert_simp, tri_ind_simp, num_tri_simp, elev_ang_low_lim, mask, hori_fill, ray_org_elev,
+                                 opts, nullptr, stats);
+}
+
+int hz_horizon_gridded_ex(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
+                          const float *vec_north, int offset_0, int offset_1, float *hori_buffer,
+                          int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                          const char *ray_algorithm, const char *geom_type, const float *vert_simp,
+                          int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
+                          float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
+                          const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
     Timer t; t.start();
     const bool verbose = opts && opts->verbose;
     if (verbose) {   // horizon_comp.cpp:643-645 (the engine named there is Embree)
@@ -1161,9 +1206,9 @@ int hz_horizon_gridded(const float *vert_grid, int dem_dim_0, int dem_dim_1, con
         printf("BVH build time: %g s\n", local.t_bvh_s);
         printf("Total initialisation time: %g s\n", t.stop());
     }
-    rc = hz_horizon_gridded_scene(scene, vec_norm, vec_north, offset_0, offset_1, hori_buffer, dim_in_0,
-                                  dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
-                                  elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, &local);
+    rc = hz_horizon_gridded_scene_ex(scene, vec_norm, vec_north, offset_0, offset_1, hori_buffer, dim_in_0,
+                                     dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                                     elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
     hz_scene_destroy(scene);   // the reference also releases the scene per call, horizon_comp.cpp:813-814
     local.t_total_s = t.stop();
     if (verbose) {   // :818-820
@@ -1256,6 +1301,31 @@ int hz_visible_sky_fraction(const float *azim, const float *hori, const float *v
 int hz_topographic_openness(const float *azim, const float *hori, int len_0, int len_1, int len_2, float *top,
                             int device) {
     return topo_api(2, azim, hori, nullptr, len_0, len_1, len_2, top, device);
+}
+
+int hz_topo_params(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
+                   float *svf, float *vsf, float *openness, int device) {
+    const bool tilt = svf || vsf;
+    if (!svf && !vsf && !openness) return set_error(HZ_ERR_ARG, "no output requested (svf, vsf and openness are NULL)");
+    if (!azim || !hori || (tilt && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
+    if (len_0 <= 0 || len_1 <= 0 || len_2 < (tilt ? 2 : 1)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
+    int rc = select_device(device);
+    if (rc) return rc;
+    hipStream_t st = nullptr;
+    const size_t ncell = (size_t)len_0 * len_1;
+    DevIn<float> d_azim, d_hori, d_tilt;
+    DevOut<float> d_svf, d_vsf, d_open;
+    if ((rc = d_azim.bind(azim, (size_t)len_2, st))) return rc;
+    if ((rc = d_hori.bind(hori, ncell * (size_t)len_2, st))) return rc;
+    if (tilt) if ((rc = d_tilt.bind(vec_tilt, ncell * 3, st))) return rc;
+    if ((rc = d_svf.bind(svf, svf ? ncell : 0))) return rc;
+    if ((rc = d_vsf.bind(vsf, vsf ? ncell : 0))) return rc;
+    if ((rc = d_open.bind(openness, openness ? ncell : 0))) return rc;
+    if ((rc = topo_multi_launch(d_azim.dev, d_hori.dev, d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st)))
+        return rc;
+    if ((rc = d_svf.finish(st)) || (rc = d_vsf.finish(st)) || (rc = d_open.finish(st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    return HZ_OK;
 }
 
 // ---------------------------------------------------------------------------------------

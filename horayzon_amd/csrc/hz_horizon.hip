@@ -896,6 +896,137 @@ __global__ __launch_bounds__(256) void k_topo_wide(const float *__restrict__ azi
     out[c] = (float)(((double)azim_spac / (2.0 * 3.14159265358979323846)) * (double)agg);
 }
 
+// ---------------------------------------------------------------------------------------
+// Fused reductions: any subset WANT of {HZ_TOPO_SVF, HZ_TOPO_VSF, HZ_TOPO_OPEN} from ONE read of each block of `hori` (the
+// horizon call's per-chunk launch with hz_topo_out, hz_topo_params).  Same blocking, prefetch and sine / cosine table as
+// k_topo.  Every output keeps its own float32 accumulator and exactly the operation sequence of k_topo<KIND>: SVF and VSF share
+// the sine / cosine pair of the horizon angle and the tilted-plane test, which are the same operations in k_topo<0> and
+// k_topo<1>; openness adds the raw hv in float64 as k_topo<2> does.  So each fused output is bit-identical to the
+// single-output kernel on the same input (-ffp-contract=off: no multiply-add is formed in one and not in the other).
+// Only subsets of two or more outputs are instantiated; a single output launches k_topo<KIND> (topo_multi_launch).
+// ---------------------------------------------------------------------------------------
+#define HZ_TOPO_SVF 1
+#define HZ_TOPO_VSF 2
+#define HZ_TOPO_OPEN 4
+template <int WANT>
+__global__ __launch_bounds__(256, HZ_TOPO_WG) void k_topo_multi(const float *__restrict__ azim, const float *__restrict__ hori,
+                                                   const float *__restrict__ vec_tilt, size_t ncell, int A,
+                                                   float *__restrict__ out_svf, float *__restrict__ out_vsf,
+                                                   float *__restrict__ out_open) {
+    constexpr bool TILT = (WANT & (HZ_TOPO_SVF | HZ_TOPO_VSF)) != 0;
+    extern __shared__ float topo_lds[];                 // [2 A] sin / cos of the azimuths, then 4 x [64][33] blocks
+    float *az_tab = topo_lds;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float *tile = topo_lds + 2 * A + wave * (64 * (HZ_TOPO_CH + 1));
+    if (TILT) {
+        for (int k = threadIdx.x; k < A; k += blockDim.x) {
+            az_tab[k] = (float)sin((double)azim[k]);
+            az_tab[A + k] = (float)cos((double)azim[k]);
+        }
+    }
+    const size_t cell0 = ((size_t)blockIdx.x * 4 + wave) * 64;
+    const size_t c = cell0 + lane;
+    const bool have = c < ncell;
+    float tx = 0.0f, ty = 0.0f, tz = 1.0f;
+    if (TILT && have) { tx = vec_tilt[3 * c]; ty = vec_tilt[3 * c + 1]; tz = vec_tilt[3 * c + 2]; }
+    const float qx = -tx / tz, qy = -ty / tz;
+    const double half_pi = 3.14159265358979323846 / 2.0;
+    const float half_pi_f = 1.57079632679489661923f;
+    float agg_svf = 0.0f, agg_vsf = 0.0f, agg_open = 0.0f;
+    const int half = lane >> 5, col = lane & 31;
+    const size_t n_rows = cell0 < ncell ? min((size_t)64, ncell - cell0) : 0;
+    const float *src = hori + (cell0 + half) * (size_t)A + col;
+    float pre[32];
+    auto fetch = [&](int k0) {
+        const int n = min(HZ_TOPO_CH, A - k0);
+#pragma unroll
+        for (int r = 0; r < 32; r++) {
+            pre[r] = 0.0f;
+            if (col < n && (size_t)(2 * r + half) < n_rows) pre[r] = src[(size_t)(2 * r) * A + k0];
+        }
+    };
+    fetch(0);
+    __syncthreads();                                    // az_tab is written
+    for (int k0 = 0; k0 < A; k0 += HZ_TOPO_CH) {
+        const int n = min(HZ_TOPO_CH, A - k0);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int r = 0; r < 32; r++) tile[(2 * r + half) * (HZ_TOPO_CH + 1) + col] = pre[r];
+        if (k0 + HZ_TOPO_CH < A) fetch(k0 + HZ_TOPO_CH);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (!have) continue;
+        const float *row = tile + lane * (HZ_TOPO_CH + 1);
+#pragma unroll HZ_TOPO_UNROLL
+        for (int kk = 0; kk < n; kk++) {
+            const float hv = row[kk];
+            if (WANT & HZ_TOPO_OPEN) agg_open = (float)(((double)agg_open + half_pi) - (double)hv);      // k_topo<2>
+            if (!TILT) continue;
+            const float as = az_tab[k0 + kk], ac = az_tab[A + k0 + kk];
+            const float xf = as * qx + ac * qy;
+            float sn, cs;
+            hz_sincos_halfpi_f(hv, sn, cs);
+            float he = hv;
+            if (!(sn >= xf * cs)) {
+                const float hp = atanf(xf);
+                if (!(hv >= hp)) {
+                    he = hp;
+                    const float rc = __builtin_amdgcn_rsqf(1.0f + xf * xf);
+                    cs = rc; sn = xf * rc;
+                }
+            }
+            if (WANT & HZ_TOPO_SVF) agg_svf = agg_svf + ((tx * as + ty * ac) * ((half_pi_f - he) - sn * cs) + tz * (cs * cs));
+            if (WANT & HZ_TOPO_VSF) agg_vsf = agg_vsf + (1.0f - sn);
+        }
+    }
+    if (!have) return;
+    if (WANT & HZ_TOPO_OPEN) out_open[c] = agg_open / (float)A;
+    if (TILT) {
+        const float azim_spac = azim[1] - azim[0];
+        if (WANT & HZ_TOPO_SVF) out_svf[c] = (float)(((double)azim_spac / (2.0 * 3.14159265358979323846)) * (double)agg_svf);
+        if (WANT & HZ_TOPO_VSF) out_vsf[c] = (float)(((double)azim_spac / (2.0 * 3.14159265358979323846)) * (double)agg_vsf);
+    }
+}
+
+// the fused form of k_topo_wide (LDS too small for the table, or hz_debug_set("topo_wide", 1)): each output bit-identical to
+// k_topo_wide<KIND>
+template <int WANT>
+__global__ __launch_bounds__(256) void k_topo_multi_wide(const float *__restrict__ azim, const float *__restrict__ hori,
+                                                        const float *__restrict__ vec_tilt, size_t ncell, int A,
+                                                        float *__restrict__ out_svf, float *__restrict__ out_vsf,
+                                                        float *__restrict__ out_open) {
+    constexpr bool TILT = (WANT & (HZ_TOPO_SVF | HZ_TOPO_VSF)) != 0;
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncell) return;
+    float tx = 0.0f, ty = 0.0f, tz = 1.0f;
+    if (TILT) { tx = vec_tilt[3 * c]; ty = vec_tilt[3 * c + 1]; tz = vec_tilt[3 * c + 2]; }
+    const float *h = hori + c * (size_t)A;
+    float agg_svf = 0.0f, agg_vsf = 0.0f, agg_open = 0.0f;
+    for (int k = 0; k < A; k++) {
+        const float hv = h[k];
+        if (WANT & HZ_TOPO_OPEN) agg_open = (float)(((double)agg_open + (3.14159265358979323846 / 2.0)) - (double)hv);
+        if (!TILT) continue;
+        const float as = (float)sin((double)azim[k]);
+        const float ac = (float)cos((double)azim[k]);
+        const float hori_plane = (float)atan((double)(-as * tx / tz - ac * ty / tz));
+        const float he = (hv >= hori_plane) ? hv : hori_plane;
+        if (WANT & HZ_TOPO_SVF) {
+            const double ce = cos((double)he);
+            agg_svf = (float)((double)agg_svf + ((double)(tx * as + ty * ac)
+                              * ((3.14159265358979323846 / 2.0) - (double)he - (sin(2.0 * (double)he) / 2.0))
+                              + (double)tz * (ce * ce)));
+        }
+        if (WANT & HZ_TOPO_VSF) agg_vsf = (float)((double)agg_vsf + (1.0 - cos((3.14159265358979323846 / 2.0) - (double)he)));
+    }
+    if (WANT & HZ_TOPO_OPEN) out_open[c] = agg_open / (float)A;
+    if (TILT) {
+        const float azim_spac = azim[1] - azim[0];
+        if (WANT & HZ_TOPO_SVF) out_svf[c] = (float)(((double)azim_spac / (2.0 * 3.14159265358979323846)) * (double)agg_svf);
+        if (WANT & HZ_TOPO_VSF) out_vsf[c] = (float)(((double)azim_spac / (2.0 * 3.14159265358979323846)) * (double)agg_vsf);
+    }
+}
+
 int topo_launch(int kind, const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
                 int len_2, float *out, hipStream_t st) {
     const size_t ncell = (size_t)len_0 * len_1;
@@ -922,6 +1053,42 @@ int topo_launch(int kind, const float *azim, const float *hori, const float *vec
 int svf_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
                int len_2, float *svf, hipStream_t st) {
     return topo_launch(0, azim, hori, vec_tilt, len_0, len_1, len_2, svf, st);
+}
+
+template <int WANT>
+static void topo_multi_one(bool wide, size_t lds, const float *azim, const float *hori, const float *vec_tilt, size_t ncell,
+                           int A, float *svf, float *vsf, float *openness, hipStream_t st) {
+    const dim3 grid((unsigned)((ncell + 255) / 256)), block(256);
+    if (wide) hipLaunchKernelGGL(k_topo_multi_wide<WANT>, grid, block, 0, st, azim, hori, vec_tilt, ncell, A, svf, vsf, openness);
+    else hipLaunchKernelGGL(k_topo_multi<WANT>, grid, block, lds, st, azim, hori, vec_tilt, ncell, A, svf, vsf, openness);
+}
+
+int topo_multi_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
+                      float *svf, float *vsf, float *openness, hipStream_t st) {
+    const int want = (svf ? HZ_TOPO_SVF : 0) | (vsf ? HZ_TOPO_VSF : 0) | (openness ? HZ_TOPO_OPEN : 0);
+    switch (want) {                     // one output: the single-output kernel itself (the SVF-only horizon call stays k_topo<0>)
+        case 0: return set_error(HZ_ERR_ARG, "no reduction requested");
+        case HZ_TOPO_SVF: return topo_launch(0, azim, hori, vec_tilt, len_0, len_1, len_2, svf, st);
+        case HZ_TOPO_VSF: return topo_launch(1, azim, hori, vec_tilt, len_0, len_1, len_2, vsf, st);
+        case HZ_TOPO_OPEN: return topo_launch(2, azim, hori, vec_tilt, len_0, len_1, len_2, openness, st);
+        default: break;
+    }
+    const size_t ncell = (size_t)len_0 * len_1;
+    if (ncell == 0) return HZ_OK;
+    const size_t lds = (2 * (size_t)len_2 + 4 * 64 * (HZ_TOPO_CH + 1)) * sizeof(float);
+    const bool wide = !(lds <= 60 * 1024 && g_topo_wide.load(std::memory_order_relaxed) == 0);      // as topo_launch
+    switch (want) {
+        case HZ_TOPO_SVF | HZ_TOPO_VSF:
+            topo_multi_one<HZ_TOPO_SVF | HZ_TOPO_VSF>(wide, lds, azim, hori, vec_tilt, ncell, len_2, svf, vsf, openness, st); break;
+        case HZ_TOPO_SVF | HZ_TOPO_OPEN:
+            topo_multi_one<HZ_TOPO_SVF | HZ_TOPO_OPEN>(wide, lds, azim, hori, vec_tilt, ncell, len_2, svf, vsf, openness, st); break;
+        case HZ_TOPO_VSF | HZ_TOPO_OPEN:
+            topo_multi_one<HZ_TOPO_VSF | HZ_TOPO_OPEN>(wide, lds, azim, hori, vec_tilt, ncell, len_2, svf, vsf, openness, st); break;
+        default:
+            topo_multi_one<HZ_TOPO_SVF | HZ_TOPO_VSF | HZ_TOPO_OPEN>(wide, lds, azim, hori, vec_tilt, ncell, len_2, svf, vsf, openness, st); break;
+    }
+    HZ_HIP(hipGetLastError());
+    return HZ_OK;
 }
 
 }  // namespace hz

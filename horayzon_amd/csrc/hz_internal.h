@@ -176,6 +176,10 @@ int topo_launch(int kind, const float *azim, const float *hori, const float *vec
                 int len_2, float *out, hipStream_t st);
 int svf_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
                int len_2, float *svf, hipStream_t st);
+// any subset of the three reductions from one pass over `hori`: the outputs that are not NULL are written (at least one;
+// vec_tilt is read when svf or vsf is); a single output launches k_topo<KIND> itself
+int topo_multi_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
+                      float *svf, float *vsf, float *openness, hipStream_t st);
 
 // hz_near.hip: near-field certificates (pre-pass of the horizon kernel)
 struct NearArgs {

@@ -11,8 +11,9 @@ import numpy as np
 
 from . import _lib
 from . import _validate as V
-from ._lib import Scene, hz_opts, hz_stats, ptr
+from ._lib import Scene, hz_opts, hz_stats, hz_topo_out, ptr
 
+TOPO_NAMES = ("svf", "vsf", "openness")     # the reductions `topo=` can ask for (hz_opts.svf, hz_topo_out.vsf / .openness)
 last_stats = None   # hz_stats of the most recent call as a dict (timers, ray count)
 # test hook: defaults of the launch-schedule options ("left_min", "persist_grid", "left_cap_test": hz_opts) for calls that do not
 # pass them -- lets the parity tests run their cases under other schedules without touching every call
@@ -39,6 +40,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     num_tri_simp=1, elev_ang_low_lim=-15.0, mask=None,
                     hori_fill=0.0, ray_org_elev=0.01, *, device=0, verbose=False,
                     scene=None, svf_vec_tilt=None, svf_only=False, rows=None, count_work=False, devices=None,
+                    topo=None, topo_vec_tilt=None, topo_only=False,
                     _top_nodes=-1, _regroup=-1, _hit_cache=True, _chunk_rows=0, _near_skip=True, _level_stack=False,
                     _verify_near=False, _left_min=0, _persist_grid=0):
     """Horizon computation for gridded domain.
@@ -59,7 +61,12 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     entry, balanced by ``mask``, and each slab is computed by its own host thread on its own
     GPU -- the scene is built per device, nothing is exchanged, every thread copies its rows
     straight into the returned array; the multi-process form of the same sharding is
-    ``horayzon_amd.dist``).
+    ``horayzon_amd.dist``), ``topo`` (names from ``TOPO_NAMES``: the sky view factor, visible sky
+    fraction and positive topographic openness are reduced from the horizon in the same call, one
+    launch per horizon chunk, and returned as a third value ``{name: float32 (y, x)}``; "svf" and
+    "vsf" need ``topo_vec_tilt``, the tilted normals; with ``topo_only`` the horizon is never
+    materialised and ``None`` is returned in its place; each map is bit-identical to the
+    ``topo_param`` function applied to the returned horizon).
     """
     global last_stats
     _check_f32(vert_grid, 1, "vert_grid")
@@ -94,6 +101,25 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
         (ValueError, "vertex buffer vert_simp is larger than 16 GB", lambda: vert_simp.nbytes > 16.0e9),
     ))
 
+    # further reductions in the same call (not in the reference): checked before anything reaches the library
+    names = None if topo is None else ([topo] if isinstance(topo, str) else list(topo))
+    tilted = names is not None and ("svf" in names or "vsf" in names)
+    if topo_vec_tilt is not None:
+        _check_f32(topo_vec_tilt, 3, "topo_vec_tilt")
+    V.run((
+        (ValueError, "'topo_only' needs 'topo'", lambda: topo_only and names is None),
+        (ValueError, "'topo' cannot be combined with 'svf_vec_tilt' or 'svf_only' (ask for \"svf\" in 'topo')",
+         lambda: names is not None and (svf_vec_tilt is not None or svf_only)),
+        (ValueError, "'topo' is empty", lambda: names is not None and not names),
+        (ValueError, "unknown name(s) in 'topo': %r (choose from %r)" % (
+            [n for n in (names or ()) if n not in TOPO_NAMES], TOPO_NAMES),
+         lambda: any(n not in TOPO_NAMES for n in names or ())),
+        (ValueError, "'svf' and 'vsf' in 'topo' need 'topo_vec_tilt'", lambda: tilted and topo_vec_tilt is None),
+        (ValueError, "'svf' and 'vsf' in 'topo' need azim_num >= 2", lambda: tilted and azim_num < 2),
+        (ValueError, "shape of topo_vec_tilt is inconsistent with vec_norm",
+         lambda: topo_vec_tilt is not None and topo_vec_tilt.shape != vec_norm.shape),
+    ))
+
     # Ensure that passed arrays are contiguous in memory (horizon.pyx:159-163)
     vert_grid = np.ascontiguousarray(vert_grid)
     vec_norm = np.ascontiguousarray(vec_norm)
@@ -106,7 +132,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     # Allocate horizon array (horizon.pyx:170-173)
     if svf_only and svf_vec_tilt is None:
         raise ValueError("'svf_only' needs 'svf_vec_tilt'")
-    hori_buffer = None if svf_only else np.empty((dim_in_0, dim_in_1, azim_num), dtype=np.float32)
+    hori_buffer = None if (svf_only or topo_only) else np.empty((dim_in_0, dim_in_1, azim_num), dtype=np.float32)
     if rows is not None and hori_buffer is not None:
         hori_buffer.fill(np.nan)   # only a slab is written; every cell is written otherwise
                                    # (masked ones get hori_fill), so the 18 GB pre-fill is skipped
@@ -130,7 +156,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     if n_verify < 0 or n_verify != _verify_near:
         raise ValueError("_verify_near must be a non-negative integer (or a bool)")
     opts.verify_near = n_verify
-    opts.skip_hori = 1 if svf_only else 0
+    opts.skip_hori = 1 if (svf_only or topo_only) else 0
     opts.count_work = int(bool(count_work))
     if rows is not None:
         if len(rows) != 2 or not (0 <= int(rows[0]) < int(rows[1]) <= dim_in_0):
@@ -147,24 +173,37 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
         svf = np.full((dim_in_0, dim_in_1), np.nan, dtype=np.float32)
         opts.svf = ptr(svf)
         opts.vec_tilt = ptr(svf_vec_tilt)
+    maps, topo_out = None, None
+    if names is not None:
+        # NaN outside a row slab, as for the SVF; "svf" goes through hz_opts.svf, the others through hz_topo_out
+        maps = {n: np.full((dim_in_0, dim_in_1), np.nan, dtype=np.float32) for n in TOPO_NAMES if n in names}
+        if tilted:
+            topo_vec_tilt = np.ascontiguousarray(topo_vec_tilt)
+            opts.vec_tilt = ptr(topo_vec_tilt)
+        if "svf" in maps:
+            opts.svf = ptr(maps["svf"])
+        if "vsf" in maps or "openness" in maps:
+            topo_out = hz_topo_out(ptr(maps.get("vsf")), ptr(maps.get("openness")))
     stats = hz_stats()
     L = _lib.lib()
 
     def run(o, st):
+        # (the _ex entry points only when hz_topo_out has a map: every other call reaches the library as before)
+        ex = () if topo_out is None else (C.byref(topo_out),)
         if scene is None:
-            return L.hz_horizon_gridded(
+            return (L.hz_horizon_gridded_ex if ex else L.hz_horizon_gridded)(
                 ptr(vert_grid), dem_dim_0, dem_dim_1, ptr(vec_norm), ptr(vec_north),
                 offset_0, offset_1, ptr(hori_buffer), dim_in_0, dim_in_1, azim_num,
                 dist_search, hori_acc, ray_algorithm.encode("utf-8"),
                 geom_type.encode("utf-8"), ptr(vert_simp), num_vert_simp,
                 ptr(tri_ind_simp), num_tri_simp, elev_ang_low_lim, ptr(mask),
-                hori_fill, ray_org_elev, C.byref(o), C.byref(st))
+                hori_fill, ray_org_elev, C.byref(o), *ex, C.byref(st))
         o.device = scene.device
-        return L.hz_horizon_gridded_scene(
+        return (L.hz_horizon_gridded_scene_ex if ex else L.hz_horizon_gridded_scene)(
             scene._h, ptr(vec_norm), ptr(vec_north), offset_0, offset_1,
             ptr(hori_buffer), dim_in_0, dim_in_1, azim_num, dist_search, hori_acc,
             ray_algorithm.encode("utf-8"), elev_ang_low_lim, ptr(mask), hori_fill,
-            ray_org_elev, C.byref(o), C.byref(st))
+            ray_org_elev, C.byref(o), *ex, C.byref(st))
 
     if devices is None:
         rc = run(opts, stats)
@@ -216,6 +255,8 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     for i in range(azim_num):
         azim[i] = ((2 * np.pi) / azim_num * i)
 
+    if maps is not None:
+        return hori_buffer, azim, maps
     if svf is not None:
         return hori_buffer, azim, svf
     return hori_buffer, azim

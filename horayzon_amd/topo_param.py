@@ -1,5 +1,6 @@
-"""horayzon.topo_param.sky_view_factor on MI355X (the only topo_param routine
-on the horizon hot path; reference: horayzon/topo_param.pyx:377-460)."""
+"""horayzon.topo_param on MI355X: the reductions of a horizon array (sky view factor, visible sky
+fraction, topographic openness; reference: horayzon/topo_param.pyx:377-603, and all three in one
+pass: topo_parameters) and the slope computations (:16-372)."""
 import numpy as np
 
 from . import _lib
@@ -64,6 +65,50 @@ def topographic_openness(azim, hori, *, device=0):
     _lib.check(_lib.lib().hz_topographic_openness(ptr(azim), ptr(hori), hori.shape[0], hori.shape[1],
                                                   hori.shape[2], ptr(top), device))
     return top
+
+
+TOPO_NAMES = ("svf", "vsf", "openness")
+
+
+def topo_parameters(azim, hori, vec_tilt=None, which=TOPO_NAMES, *, device=0):
+    """Any of the three reductions above -- sky view factor ("svf"), visible sky fraction ("vsf"),
+    positive topographic openness ("openness") -- from ONE pass over the horizon array
+    (hz_topo_params).  Arguments and checks as the single-output functions (topo_param.pyx:398-404,
+    :486-492, :565-569); ``vec_tilt`` is needed for "svf" and "vsf" only.  Returns
+    ``{name: float32 (y, x)}``, each map bit-identical to the single-output function's."""
+    names = [which] if isinstance(which, str) else list(which)
+    if not names:
+        raise ValueError("'which' is empty")
+    unknown = [n for n in names if n not in TOPO_NAMES]
+    if unknown:
+        raise ValueError("unknown name(s) in 'which': %r (choose from %r)" % (unknown, TOPO_NAMES))
+    tilted = "svf" in names or "vsf" in names
+    if tilted and vec_tilt is None:
+        raise ValueError("'svf' and 'vsf' need 'vec_tilt'")
+    # Check arguments (topo_param.pyx:398-404 / :565-569)
+    if tilted:
+        if (len(azim) != hori.shape[2]) or (hori.shape[:2] != vec_tilt.shape[:2])\
+                or (vec_tilt.shape[2] != 3):
+            raise ValueError("Inconsistent/incorrect shapes of input arrays")
+        if ((azim.dtype != "float32") or (hori.dtype != "float32")
+                or (vec_tilt.dtype != "float32")):
+            raise ValueError("Input array(s) has/have incorrect data type(s)")
+        if len(azim) < 2:   # azim[1] - azim[0] is read (topo_param.pyx:433, :520)
+            raise ValueError("Inconsistent/incorrect shapes of input arrays")
+        vec_tilt = np.ascontiguousarray(vec_tilt)
+    else:
+        if len(azim) != hori.shape[2]:
+            raise ValueError("Inconsistent/incorrect shapes of input arrays")
+        if (azim.dtype != "float32") or (hori.dtype != "float32"):
+            raise ValueError("Input array(s) has/have incorrect data type(s)")
+        vec_tilt = None
+    azim = np.ascontiguousarray(azim)
+    hori = np.ascontiguousarray(hori)
+    out = {n: np.empty(hori.shape[:2], dtype=np.float32) for n in TOPO_NAMES if n in names}
+    _lib.check(_lib.lib().hz_topo_params(ptr(azim), ptr(hori), ptr(vec_tilt), hori.shape[0], hori.shape[1],
+                                         hori.shape[2], ptr(out.get("svf")), ptr(out.get("vsf")),
+                                         ptr(out.get("openness")), device))
+    return out
 
 
 def _slope(which, x, y, z, rot_mat, output_rot, device):

@@ -52,7 +52,8 @@ typedef struct hz_opts {
                            /*   that blocked the cell's previous ray; 1: always start at the root */
     float  *svf;           /* optional fused sky view factor out, f32[y][x]    */
     const float *vec_tilt; /* tilted normals f32[y][x][3] for svf              */
-    int32_t skip_hori;     /* 1: hori_buffer may be NULL, only svf is written  */
+    int32_t skip_hori;     /* 1: hori_buffer may be NULL, only svf (and the    */
+                           /*   maps of hz_topo_out, _ex calls) are written    */
     int32_t chunk_rows;    /* rows per launch when hori is host memory or skipped (chunks are      */
                            /*   double buffered and copied out while the next one is traced);      */
                            /*   <= 0: as many rows as fit 4 GiB                                     */
@@ -114,7 +115,8 @@ typedef struct hz_stats {
     uint64_t wave_node_iters; /* count_work: wave-level executions of the node  */
     uint64_t wave_leaf_iters; /*   step / leaf step / ray refill section (SIMT  */
     uint64_t wave_refills;    /*   efficiency = lane count / (64 x wave count)) */
-    double t_svf_s;        /* sky-view-factor kernel (when opts.svf is set)    */
+    double t_svf_s;        /* the horizon reductions: the kernel that writes opts.svf and / or the  */
+                           /*   hz_topo_out maps of the _ex calls (one launch per horizon chunk)      */
     uint64_t stack_fallbacks; /* launches after which blocks (or the whole launch) were repeated with the one-entry-per- */
                               /*   level stack because a ray ran out of entries of the fast one                          */
     uint64_t rays_shortened;  /* count_work: rays that started beyond the cell's neighbourhood (near-field certificate) */
@@ -201,6 +203,42 @@ int hz_horizon_gridded_scene(const hz_scene *scene,
                              float hori_fill, float ray_org_elev,
                              const hz_opts *opts, hz_stats *stats);
 
+/* Further reductions of the horizon computed in the same call (the _ex forms below).  Each map follows every   */
+/* rule opts->svf follows: host or device memory; only the row slab is written (other rows are left untouched);  */
+/* with opts->hori_is_slab it addresses row_begin; opts->vec_tilt (opts->inputs_are_slab) supplies the tilt.     */
+/* Every horizon chunk gets ONE reduction launch that writes all requested maps, opts->svf included, and          */
+/* opts->skip_hori is valid as soon as any of svf / vsf / openness is requested.                                 */
+typedef struct hz_topo_out {
+    int32_t size;          /* sizeof(hz_topo_out); other values -> HZ_ERR_ARG (room to grow without a new revision)  */
+    float  *vsf;           /* optional visible sky fraction f32[y][x] (_visible_sky_fraction_cy, topo_param.pyx:499-543); */
+                           /*   needs opts->vec_tilt and azim_num >= 2                                                */
+    float  *openness;      /* optional positive topographic openness f32[y][x] [radian] (_topographic_openness_cy,   */
+                           /*   :577-603); needs neither vec_tilt nor two azimuths                                     */
+} hz_topo_out;
+
+/* hz_horizon_gridded / hz_horizon_gridded_scene plus the maps of `topo`.  topo == NULL, or both of its pointers */
+/* NULL: exactly the call without _ex.                                                                           */
+int hz_horizon_gridded_ex(const float *vert_grid, int dem_dim_0, int dem_dim_1,
+                          const float *vec_norm, const float *vec_north,
+                          int offset_0, int offset_1,
+                          float *hori_buffer, int dim_in_0, int dim_in_1,
+                          int azim_num, float dist_search, float hori_acc,
+                          const char *ray_algorithm, const char *geom_type,
+                          const float *vert_simp, int num_vert_simp,
+                          const int32_t *tri_ind_simp, int num_tri_simp,
+                          float elev_ang_low_lim, const uint8_t *mask,
+                          float hori_fill, float ray_org_elev,
+                          const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+int hz_horizon_gridded_scene_ex(const hz_scene *scene,
+                                const float *vec_norm, const float *vec_north,
+                                int offset_0, int offset_1,
+                                float *hori_buffer, int dim_in_0, int dim_in_1,
+                                int azim_num, float dist_search, float hori_acc,
+                                const char *ray_algorithm,
+                                float elev_ang_low_lim, const uint8_t *mask,
+                                float hori_fill, float ray_org_elev,
+                                const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+
 /* Horizon (and optionally distance to the horizon) for arbitrary locations; argument list     */
 /* mirrors horizon_locations_comp (horizon_comp.h:22-34, horizon_comp.cpp:828-1094).           */
 /* coords f32[num_loc][3], vec_norm / vec_north f32[num_loc][3], ray_org_elev f32[num_loc],    */
@@ -240,6 +278,11 @@ int hz_visible_sky_fraction(const float *azim, const float *hori, const float *v
                             int len_0, int len_1, int len_2, float *vsf, int device);
 int hz_topographic_openness(const float *azim, const float *hori, int len_0, int len_1, int len_2,
                             float *top, int device);
+/* All three reductions of a materialised horizon array in one pass over it: any of svf / vsf / openness may be    */
+/* NULL, not all; vec_tilt is needed (and read) only for svf / vsf, which also need len_2 >= 2.  Each map is         */
+/* bit-identical to the single-output function's.                                                                   */
+int hz_topo_params(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
+                   float *svf, float *vsf, float *openness, int device);
 
 /* Test hooks for the hand-written build primitives (stable radix sort of uint32 pairs by key,   */
 /* exclusive prefix sum); host arrays, in place / in -> out.  Not needed by a binding.            */
