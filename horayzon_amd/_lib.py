@@ -75,6 +75,7 @@ SYMBOLS = (
     "hz_terrain_create", "hz_terrain_initialise", "hz_terrain_initialise_scene",
     "hz_terrain_shadow", "hz_terrain_sw_dir_cor", "hz_terrain_shadow_batch",
     "hz_terrain_sw_dir_cor_batch", "hz_terrain_count_work", "hz_terrain_destroy",
+    "hz_terrain_accumulate",
 )
 
 
@@ -170,6 +171,7 @@ def lib():
     L.hz_terrain_sw_dir_cor.argtypes = [vp, vp, vp, C.POINTER(hz_stats)]
     L.hz_terrain_shadow_batch.argtypes = [vp, vp, ip, vp, C.POINTER(hz_stats)]
     L.hz_terrain_sw_dir_cor_batch.argtypes = [vp, vp, ip, vp, C.POINTER(hz_stats)]
+    L.hz_terrain_accumulate.argtypes = [vp, vp, vp, ip, vp, vp, C.POINTER(hz_stats)]
     L.hz_terrain_count_work.argtypes = [vp, ip]
     L.hz_terrain_destroy.argtypes = [vp]
     for name in SYMBOLS:

@@ -28,6 +28,7 @@ int set_error(int code, const char *fmt, ...);
 // test knobs (hz_debug_set, include/horayzon_hip.h): process wide, read at every launch; results never depend on them
 extern std::atomic<int> g_shadow_fast_cap;   // entries of k_shadow_refill's fast stack (default HZ_SHADOW_FAST_CAP_DEFAULT; 0: level stack only)
 extern std::atomic<int> g_topo_wide;         // 1: the reductions over the azimuth axis use the fallback kernel k_topo_wide
+extern std::atomic<int> g_accum_chunk;       // > 0: sun positions per chunk of hz_terrain_accumulate (default 0: from the memory budget)
 
 #define HZ_HIP(expr)                                                                      \
     do {                                                                                  \
@@ -227,6 +228,14 @@ struct ShadowArgs {
 };
 int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st);
 int shadow_refrac_factor(const float *elevation, size_t n, double *out, hipStream_t st);
+// hz_terrain_accumulate (hz_shadow.hip): one chunk of a.num_sun positions traced into scratch [num_sun][cells] (a.which = 0:
+// shadow codes to a.out_u8 and, want_sw, the correction of the lit cells to a.out_f32; 1: the correction to a.out_f32), the
+// chunk added to float64 accumulators in ascending order (w: device f32[k] or null = ones), the accumulators rounded once
+int accum_trace_launch(const Scene *sc, const ShadowArgs &a, int want_sw, hipStream_t st);
+int accum_add_launch(const uint8_t *codes, const float *vals, size_t n, int k, const float *w, double *acc_sw, double *acc_lit,
+                     hipStream_t st);
+int accum_final_launch(const uint8_t *mask, size_t n, float fill, const double *acc_sw, const double *acc_lit, float *out_sw,
+                       float *out_lit, hipStream_t st);
 
 // hz_sort.hip: hand-written stable LSD radix sort (pairs) and exclusive scan, uint32
 size_t sort_temp_elems(size_t n);

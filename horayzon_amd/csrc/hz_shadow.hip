@@ -277,18 +277,20 @@ __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SHADOW_WG) void k_shadow_ref
 
 std::atomic<int> g_shadow_fast_cap{HZ_SHADOW_FAST_CAP_DEFAULT};      // hz_debug_set (hz_internal.h)
 std::atomic<int> g_topo_wide{0};
+std::atomic<int> g_accum_chunk{0};
 
-int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st) {
-    ShadowParams p;
+// Launch configuration of the refill kernels (k_shadow_refill, k_accum_refill) for one launch of a.num_sun positions:
+// parameters, dynamic LDS, grid, and whether the fast stack is used.  Returns 0 when there is nothing to launch.
+static int shadow_config(const Scene *sc, const ShadowArgs &a, ShadowParams &p, size_t &lds, dim3 &grid, bool &fast) {
     p.sv = scene_view(sc);
     p.vec_tilt = a.vec_tilt; p.vec_norm = a.vec_norm; p.surf_enl_fac = a.surf_enl_fac; p.elevation = a.elevation;
     p.mask = a.mask;
     p.offset_0 = a.offset_0; p.offset_1 = a.offset_1; p.dim_in_0 = a.dim_in_0; p.dim_in_1 = a.dim_in_1;
-    if (a.dim_in_0 <= 0 || a.dim_in_1 <= 0) return HZ_OK;
+    if (a.dim_in_0 <= 0 || a.dim_in_1 <= 0) return 0;
     const int tiles_i = (a.dim_in_0 + 15) / 16;
     p.tm = make_tile_map(tiles_i, (a.dim_in_1 + 15) / 16);
     p.suns = a.suns; p.out_stride = (size_t)a.dim_in_0 * (size_t)a.dim_in_1;
-    if (a.num_sun <= 0) return HZ_OK;
+    if (a.num_sun <= 0) return 0;
     p.fill = a.sw_dir_cor_fill; p.dot_prod_min = a.dot_prod_min;
     p.refrac = (a.refrac_cor && a.refrac_fac != nullptr) ? 1 : 0; p.which = a.which; p.refrac_fac = a.refrac_fac;
     p.out_u8 = a.out_u8; p.out_f32 = a.out_f32;
@@ -301,9 +303,9 @@ int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st) {
     const int fast_cap_env = g_shadow_fast_cap.load(std::memory_order_relaxed);      // (hz_debug_set("shadow_fast_cap", n): tests)
     const int height = std::max(sc->hdr.height, 1);
     const int fast_cap = std::min(fast_cap_env, 3 * height + 1);
-    const bool fast = fast_cap >= 5 && fast_cap >= height;
+    fast = fast_cap >= 5 && fast_cap >= height;
     p.stack_cap = fast ? fast_cap : 0;
-    const size_t lds = fast ? (size_t)(fast_cap + 2) * HZ_TPB * 4 : (size_t)p.stack_bytes;
+    lds = fast ? (size_t)(fast_cap + 2) * HZ_TPB * 4 : (size_t)p.stack_bytes;
     // blocks per wave: as many as leave >= ~48 workgroups per CU over the whole launch (measured on the 3601^2 tile, 144
     // positions per launch: 2 / 4 / 8 / 16 / 32 / 64 blocks -> 1.64 / 1.49 / 1.42 / 1.36 / 1.29 / 1.51 ms per position; a single
     // position: 1 / 2 / 4 / 8 / 16 blocks -> 2.49 / 1.77 / 1.67 / 1.65 / 1.79 ms, k_shadow 2.52 ms)
@@ -320,13 +322,185 @@ int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st) {
         p.tm = make_tile_map(tiles_i, (tiles_j + nb - 1) / nb);
     }
     // grid.x is a multiple of 8, so the workgroup -> XCD assignment (flat id % 8) is the same for every grid.y row
-    const dim3 grid((unsigned)(p.tm.per_xcd * 8), (unsigned)a.num_sun);
-#define HZ_LAUNCH_SHADOW(K) do { \
+    grid = dim3((unsigned)(p.tm.per_xcd * 8), (unsigned)a.num_sun);
+    return 1;
+}
+
+#define HZ_LAUNCH_REFILL(K, P) do { \
         HZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(K, grid, dim3(HZ_TPB), lds, st, p); } while (0)
-    if (fast) { if (a.count_work) HZ_LAUNCH_SHADOW((k_shadow_refill<true, true>)); else HZ_LAUNCH_SHADOW((k_shadow_refill<false, true>)); }
-    else { if (a.count_work) HZ_LAUNCH_SHADOW((k_shadow_refill<true, false>)); else HZ_LAUNCH_SHADOW((k_shadow_refill<false, false>)); }
-#undef HZ_LAUNCH_SHADOW
+        hipLaunchKernelGGL(K, grid, dim3(HZ_TPB), lds, st, P); } while (0)
+
+int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st) {
+    ShadowParams p;
+    size_t lds = 0; dim3 grid; bool fast = false;
+    if (!shadow_config(sc, a, p, lds, grid, fast)) return HZ_OK;
+    if (fast) { if (a.count_work) HZ_LAUNCH_REFILL((k_shadow_refill<true, true>), p); else HZ_LAUNCH_REFILL((k_shadow_refill<false, true>), p); }
+    else { if (a.count_work) HZ_LAUNCH_REFILL((k_shadow_refill<true, false>), p); else HZ_LAUNCH_REFILL((k_shadow_refill<false, false>), p); }
+    HZ_HIP(hipGetLastError());
+    return HZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Terrain.accumulate (hz_terrain_accumulate): weighted sums over many sun positions without a map per position.
+//
+// Positions go in chunks of K.  k_accum_refill traces one chunk into scratch [K][cells] -- with the sunlit sum wanted, the
+// shadow code (u8; which = 0: one ray per cell with dot_ts > 0, the shadow_batch ray set) and, if the correction sum is also
+// wanted, the correction factor of the lit cells (f32); with the correction sum alone, the correction factor (which = 1:
+// one ray per cell with dot_ts > dot_prod_min, the sw_dir_cor_batch ray set).  Because dot_prod_min > 0 (ang_max <= 89.99)
+// the second ray set is a subset of the first and one ray serves both sums.  k_accum_add then adds the chunk to per-cell
+// float64 accumulators in ascending position order, and k_accum_final rounds them to float32 once and writes the fill
+// value to masked cells.
+//
+// k_accum_refill is k_shadow_refill's loop with another result step.  It is a kernel of its own, not a template parameter
+// of k_shadow_refill: k_shadow_refill<false, true> is one of the kernels whose device assembly stamps profiles/*.json
+// (scripts/kernel_asm.py), and its machine code must not move.
+struct AccumParams {
+    ShadowParams s;          // s.which = 0: shadow codes to s.out_u8 (+ correction of the lit cells to s.out_f32); 1: correction only
+    int want_sw;             // s.which == 0: also write the correction factor
+};
+
+// result of a traced ray: the code and value Terrain.shadow / Terrain.sw_dir_cor give for the cell (shadow_result)
+__device__ __forceinline__ void accum_result(const AccumParams &p, size_t cell, bool hit, const ShadowRay &r,
+                                             uint8_t *out_u8, float *out_f32) {
+    if (p.s.which != 0) { shadow_result(p.s, cell, hit, r, out_u8, out_f32); return; }
+    out_u8[cell] = hit ? 2 : 0;
+    if (!p.want_sw || hit) return;        // (k_accum_add reads the correction of code-0 cells only)
+    float v = 0.0f;                       // a lit cell with dot_ts <= dot_prod_min: shadow_setup's which = 1 branch
+    if (r.dot_ts > p.s.dot_prod_min) {
+        float dot_prod_ns = r.dot_ns;
+        if (dot_prod_ns < p.s.dot_prod_min) dot_prod_ns = p.s.dot_prod_min;
+        v = (r.dot_ts / dot_prod_ns) * p.s.surf_enl_fac[cell];
+    }
+    out_f32[cell] = v;
+}
+
+template <bool COUNT, bool FAST>
+__global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SHADOW_WG) void k_accum_refill(AccumParams ap) {
+    const ShadowParams &p = ap.s;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int *stack = reinterpret_cast<int *>(smem + (FAST ? 2 * HZ_TPB * 4 : 0));
+    const int tid = threadIdx.x;
+    int ti = 0, tj = 0;
+    const bool has_tile = hz_tile_of_block(p.tm, blockIdx.x, &ti, &tj);
+    const int wave = tid >> 6, lane = tid & 63;
+    const int sun_idx = blockIdx.y;
+    const float p_sun_x = p.suns[3 * sun_idx], p_sun_y = p.suns[3 * sun_idx + 1], p_sun_z = p.suns[3 * sun_idx + 2];
+    uint8_t *const out_u8 = p.out_u8 ? p.out_u8 + (size_t)sun_idx * p.out_stride : nullptr;
+    float *const out_f32 = p.out_f32 ? p.out_f32 + (size_t)sun_idx * p.out_stride : nullptr;
+    unsigned rays = 0;
+    TravCounters tc; tc.nodes = 0; tc.tris = 0; tc.w_nodes = 0; tc.w_leaves = 0;
+    const int i_base = ti * 16 + (wave >> 1) * 8, j_base = tj * (16 * p.nb) + (wave & 1) * 8;
+    const int total = has_tile ? 64 * p.nb : 0;
+    int next = 0;
+    bool ray_active = false;
+    ShadowRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.dot_ts = r.dot_ns = 0.0f;
+    size_t cell = 0;
+    RayBox rb = hz_raybox(0, 0, 0, 0, 0, 1);
+    TravState ts; hz_trav_reset(ts);
+    bool overflow = false;
+    for (;;) {
+        if (next < total) {
+            const unsigned long long need = __ballot(!ray_active);
+            if (need != 0ull) {
+                const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
+                const int my = next + rank;
+                next += __popcll(need);
+                if (!ray_active && my < total) {
+                    const int i = i_base + ((my & 63) >> 3), j = j_base + (my >> 6) * 16 + (my & 7);
+                    if (i < p.dim_in_0 && j < p.dim_in_1 && shadow_setup(p, i, j, p_sun_x, p_sun_y, p_sun_z, out_u8, out_f32, r)) {
+                        cell = (size_t)i * p.dim_in_1 + j;
+                        rb = hz_raybox((r.ox - p.sv.cx) - p.sv.tau * r.dx, (r.oy - p.sv.cy) - p.sv.tau * r.dy, (r.oz - p.sv.cz) - p.sv.tau * r.dz,
+                                       r.dx, r.dy, r.dz);
+                        hz_trav_reset(ts);
+                        overflow = false;
+                        ray_active = true;
+                        rays++;
+                    }
+                }
+            }
+        }
+        if (__ballot(ray_active) == 0ull) {
+            if (next >= total) break;
+            continue;
+        }
+        if (ray_active) {
+            int res = hz_trace<HZ_TPB, COUNT, 2, false, !FAST>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
+                                                    __builtin_inff(), __builtin_inff(), rb, ts, (next < total) ? HZ_SHADOW_REGROUP : 0, HZ_SHADOW_LEAF_BIAS, tc, p.stack_cap, overflow);
+            if (FAST && res != 2 && overflow) {
+                bool unused = false;
+                hz_trav_reset(ts);
+                res = hz_trace<HZ_TPB, COUNT, 2, false, true>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
+                                                                    __builtin_inff(), __builtin_inff(), rb, ts, 0, HZ_SHADOW_LEAF_BIAS, tc, 0, unused);
+                if (COUNT && p.counters) atomicAdd(&p.counters[8], 1ull);
+            }
+            if (res != 2) {
+                accum_result(ap, cell, res == 1, r, out_u8, out_f32);
+                ray_active = false;
+            }
+        }
+    }
+    shadow_counters<COUNT>(p, rays, tc, lane);
+}
+
+int accum_trace_launch(const Scene *sc, const ShadowArgs &a, int want_sw, hipStream_t st) {
+    AccumParams ap;
+    size_t lds = 0; dim3 grid; bool fast = false;
+    if (!shadow_config(sc, a, ap.s, lds, grid, fast)) return HZ_OK;
+    ap.want_sw = want_sw;
+    if (fast) { if (a.count_work) HZ_LAUNCH_REFILL((k_accum_refill<true, true>), ap); else HZ_LAUNCH_REFILL((k_accum_refill<false, true>), ap); }
+    else { if (a.count_work) HZ_LAUNCH_REFILL((k_accum_refill<true, false>), ap); else HZ_LAUNCH_REFILL((k_accum_refill<false, false>), ap); }
+    HZ_HIP(hipGetLastError());
+    return HZ_OK;
+}
+#undef HZ_LAUNCH_REFILL
+
+// One chunk of k positions into the accumulators, ascending in the position: acc += (double)w * (double)value, the product of
+// two floats exact in float64.  codes != null: the sunlit sum adds w * [code == 0], the correction sum w * (code == 0 ?
+// value : 0) (the value is written for lit cells only); codes == null: the correction sum adds w * value.  w == null: 1.
+__global__ __launch_bounds__(256) void k_accum_add(const uint8_t *__restrict__ codes, const float *__restrict__ vals, size_t n,
+                                                   int k, const float *__restrict__ w, double *__restrict__ acc_sw,
+                                                   double *__restrict__ acc_lit) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    double s = acc_sw ? acc_sw[c] : 0.0, l = acc_lit ? acc_lit[c] : 0.0;
+    for (int q = 0; q < k; q++) {
+        const double wq = w ? (double)w[q] : 1.0;
+        const size_t at = (size_t)q * n + c;
+        if (codes) {
+            const bool lit = codes[at] == 0;
+            if (acc_lit) l += wq * (lit ? 1.0 : 0.0);
+            if (acc_sw) s += wq * (double)(lit ? vals[at] : 0.0f);
+        } else {
+            s += wq * (double)vals[at];
+        }
+    }
+    if (acc_sw) acc_sw[c] = s;
+    if (acc_lit) acc_lit[c] = l;
+}
+
+// float32 once at the end; masked cells (mask != 1) get the fill value whatever was accumulated there
+__global__ __launch_bounds__(256) void k_accum_final(const uint8_t *__restrict__ mask, size_t n, float fill,
+                                                     const double *__restrict__ acc_sw, const double *__restrict__ acc_lit,
+                                                     float *__restrict__ out_sw, float *__restrict__ out_lit) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const bool on = mask[c] == 1;
+    if (out_sw) out_sw[c] = on ? (float)acc_sw[c] : fill;
+    if (out_lit) out_lit[c] = on ? (float)acc_lit[c] : fill;
+}
+
+int accum_add_launch(const uint8_t *codes, const float *vals, size_t n, int k, const float *w, double *acc_sw, double *acc_lit,
+                     hipStream_t st) {
+    if (n == 0 || k <= 0) return HZ_OK;
+    hipLaunchKernelGGL(k_accum_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, codes, vals, n, k, w, acc_sw, acc_lit);
+    HZ_HIP(hipGetLastError());
+    return HZ_OK;
+}
+
+int accum_final_launch(const uint8_t *mask, size_t n, float fill, const double *acc_sw, const double *acc_lit, float *out_sw,
+                       float *out_lit, hipStream_t st) {
+    if (n == 0) return HZ_OK;
+    hipLaunchKernelGGL(k_accum_final, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mask, n, fill, acc_sw, acc_lit, out_sw, out_lit);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }

@@ -184,3 +184,57 @@ class Terrain:
             self._h, ptr(np.ascontiguousarray(sun_positions)), sun_positions.shape[0],
             ptr(sw_dir_cor_buffers), C.byref(st)))
         self.last_stats = st.as_dict()
+
+    # --- additive: weighted sums over many sun positions, no map per position -------------------------------------
+    def _accum_arg(self, buf, ndim, name):
+        """f32 argument of ``accumulate``: a NumPy array, or a torch tensor on the Terrain's GPU."""
+        if isinstance(buf, np.ndarray):
+            _typed(buf, np.float32, ndim, name)
+            return
+        if not hasattr(buf, "data_ptr"):
+            raise TypeError("Argument '%s' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
+                            % (name, type(buf).__name__))
+        if buf.dim() != ndim:
+            raise ValueError("Buffer has wrong number of dimensions (expected %d, got %d)" % (ndim, buf.dim()))
+        if str(buf.dtype).split(".")[-1] != "float32":
+            raise ValueError("Buffer dtype mismatch, expected 'float32' but got '%s'" % buf.dtype)
+        if buf.device.type != "cuda" or buf.device.index != self.device:
+            raise ValueError("tensor '%s' is not on the Terrain's device (cuda:%d)" % (name, self.device))
+
+    def accumulate(self, sun_positions, weights=None, *, sw_dir_cor_sum=None, sunlit_sum=None):
+        """Weighted sums over sun_positions f32[S][3] (S >= 1) without a map per position:
+        ``sw_dir_cor_sum`` = sum of weights[s] * sw_dir_cor(sun_positions[s]) and ``sunlit_sum`` = sum of weights[s] over
+        the positions for which shadow() gives 0, per cell, accumulated in float64 in ascending s and rounded to float32
+        once; masked cells get ``sw_dir_cor_fill``.  weights f32[S] (None: ones).  Outputs f32[y][x], NumPy or torch
+        tensors on the Terrain's GPU; at least one.  Device memory besides the buffers does not grow with S
+        (``last_stats["scratch_bytes"]``)."""
+        outs = (("sw_dir_cor_sum", sw_dir_cor_sum), ("sunlit_sum", sunlit_sum))
+        self._accum_arg(sun_positions, 2, "sun_positions")
+        if weights is not None:
+            self._accum_arg(weights, 1, "weights")
+        for name, buf in outs:
+            if buf is not None:
+                self._accum_arg(buf, 2, name)
+        given = [buf for _, buf in outs if buf is not None]
+        arrays = [sun_positions] + ([weights] if weights is not None else []) + given
+
+        def contiguous(a):
+            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
+        V.run((
+            (ValueError, "at least one of 'sw_dir_cor_sum' and 'sunlit_sum' must be given", lambda: not given),
+            (ValueError, "array 'sun_positions' has incorrect shape",
+             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
+            (ValueError, "array 'weights' has incorrect shape",
+             lambda: weights is not None and weights.shape[0] != sun_positions.shape[0]),
+            (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in arrays)),
+            (ValueError, "'sw_dir_cor_sum' and 'sunlit_sum' must be different arrays",
+             lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
+        ))
+        for name, buf in outs:
+            if buf is not None:
+                self._check_out(buf, name)
+        st = hz_stats()
+        _lib.check(_lib.lib().hz_terrain_accumulate(
+            self._h, ptr(sun_positions), ptr(weights), sun_positions.shape[0],
+            ptr(sw_dir_cor_sum), ptr(sunlit_sum), C.byref(st)))
+        self.last_stats = st.as_dict()

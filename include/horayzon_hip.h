@@ -300,7 +300,8 @@ int hz_debug_copy_peak(int device, size_t bytes, double *gbs);
 int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* test knobs (process wide; results never depend on them): "shadow_fast_cap" = entries of the shadow kernel's fast stack (< 0: */
 /* the default; small values make the in-kernel retry with the level stack the common case), "topo_wide" = 1: the reductions    */
-/* over the azimuth axis use the one-lane-per-cell fallback kernel                                                               */
+/* over the azimuth axis use the one-lane-per-cell fallback kernel, "accum_chunk" = sun positions per chunk of                   */
+/* hz_terrain_accumulate (<= 0: the default, from the scratch budget)                                                           */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */
@@ -384,6 +385,15 @@ int hz_terrain_shadow_batch(hz_terrain *terrain, const float *sun_positions,
                             int num_sun, uint8_t *shadow_buffers, hz_stats *stats);
 int hz_terrain_sw_dir_cor_batch(hz_terrain *terrain, const float *sun_positions,
                                 int num_sun, float *sw_dir_cor_buffers, hz_stats *stats);
+/* additive: weighted sums over num_sun >= 1 positions without a map per position. For unmasked  */
+/* cells, sw_dir_cor_sum[c] = (float)(sum over s ascending of (double)w[s] * sw_dir_cor_s[c]) and  */
+/* sunlit_sum[c] = (float)(sum of (double)w[s] * [shadow_s[c] == 0]), float64 accumulators rounded */
+/* once; masked cells get sw_dir_cor_fill in both. weights f32[num_sun] (NULL = ones); an output   */
+/* NULL = not wanted (at least one). Positions, weights and outputs f32[y][x] may be host or       */
+/* device pointers. One ray per (cell, position) with dot_ts > 0 if sunlit_sum is wanted, else    */
+/* with dot_ts > dot_prod_min; device scratch (hz_stats.scratch_bytes) does not grow with num_sun  */
+int hz_terrain_accumulate(hz_terrain *terrain, const float *sun_positions, const float *weights, int num_sun,
+                          float *sw_dir_cor_sum, float *sunlit_sum, hz_stats *stats);
 /* additive: 1 = later shadow / sw_dir_cor calls run the counting instantiation and also fill   */
 /* hz_stats.nodes_visited / tris_tested / wave_*_iters (slower; for the roofline's B_trav)      */
 int hz_terrain_count_work(hz_terrain *terrain, int on);
