@@ -44,6 +44,13 @@ hori_sample_cells.npy (their row and column); the inputs are seeded, so two buil
 The flag is refused for c4, c5 and the row-sharded c3 line (`--gpus N` with N > 1, HZ_FORCE_DIST): those runs cannot be
 compared output for output this way (their SVF can be saved with --dump-svf-rows / --dump-path).
 
+A plain run does what its headline figure needs and nothing else: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the line (its roofline is the I/O view, from no run of its own).  `--full` adds what takes runs
+of its own, all untimed and outside `value`: the counter pass and the machine calibration behind the VALU roofline, the
+extras of the one-rank c3 line (the other search algorithms, the curved tile, config 4, the strong-scaling prediction,
+horizon_locations, config 5), config 5 over the same ranks and the measured scaling prediction of the N > 1 line, the
+NumPy-in / NumPy-out call and the CPU baseline; the --no-* options drop single pieces of that.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -81,6 +88,10 @@ def parse():
     ap.add_argument("--bcast", choices=("blob", "verts"), default="blob",
                     help="several ranks: broadcast the finished scene blob (vertices + LBVH), or only the 12 V bytes of "
                          "vertices and rebuild the LBVH on every rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed figures that take runs of their own (counter passes, machine calibration, extras, "
+                         "config 5 over the same ranks, the NumPy-in / NumPy-out call, the CPU baseline); the --no-* options "
+                         "below drop single pieces of it")
     ap.add_argument("--no-e2e", action="store_true", help="c3: skip the untimed NumPy-in / NumPy-out call of horizon_gridded")
     ap.add_argument("--no-c5-extra", action="store_true",
                     help="c3, one rank: skip the config-5 job (14401^2 mosaic, ~2 min incl. synthesis) among the untimed extras")
@@ -113,7 +124,10 @@ def parse():
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="c3: after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64: the SVF of "
                          "its rows, the horizon at a fixed, seeded sample of its cells; at most 64 MB in all)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:       # a plain run: set-up, warm-up, the timed steps, --dump-outputs, the line
+        args.no_count = args.no_peaks = args.no_extras = args.no_e2e = args.no_c5_extra = args.no_cpu_baseline = True
+    return args
 
 
 def kernel_asm_sha():

@@ -5,7 +5,7 @@ tests/golden/embree_*.npz.  `pytest -m gpu tests/test_gpu_embree_pin.py` (HIP ke
 `pytest tests/test_oracle.py -k embree` (CPU oracle) then compare against those files and report the mismatch
 fraction against the north-star bar (1e-4 rad horizon, 1e-5 SVF).  It also records the reference's own printed
 "Ray tracing time" / ray count per case and for a band of the 3601^2 benchmark tile, the Embree / TBB libraries it ran
-with and the core count, in tests/golden/embree_timing.json -- bench.py then reports that as `cpu_baseline.embree`.
+with and the core count, in tests/golden/embree_timing.json -- bench.py --full then reports that as `cpu_baseline.embree`.
 
 The build environment of this repository has neither Embree nor a network, so the files cannot be produced here:
 until a maintainer runs this script once, parity stays "unpinned" for the ray-casting decisions.

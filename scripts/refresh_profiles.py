@@ -1,26 +1,26 @@
-"""Copy the rocprofv3 summaries of a bench run from gpurun_out/ into profiles/<round>/ and recompute
+"""Copy the rocprofv3 summaries of a bench run (scripts/profile_bench.sh) from <outdir> into profiles/<round>/ and recompute
 profiles/traffic.json (HBM bytes of k_horizon per launch) and profiles/valu_model.json (wave-level VALU
 instructions per wave iteration, calibrated on SQ_INSTS_VALU), both stamped with the hash of the kernels' device assembly
 (scripts/kernel_asm.py) they were measured for -- bench.py refuses them when the machine code changed.  "The traversal" is the
 production instantiation of k_horizon PLUS its follow-up launch (LEFT) of the same step: their counters are added up.
-usage: refresh_profiles.py <prefix> <round>, e.g. prof2 r02"""
+usage: refresh_profiles.py <prefix> <round> <outdir>, e.g. prof2 r02 prof_out"""
 import csv, glob, json, os, shutil, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
-pre, rnd = sys.argv[1], sys.argv[2]
+pre, rnd, src = sys.argv[1], sys.argv[2], sys.argv[3]
 os.makedirs("profiles/%s" % rnd, exist_ok=True)
 sha = bench.kernel_asm_sha()
-newest = lambda pat: max(glob.glob(pat), key=os.path.getmtime)       # gpurun_out/ keeps the files of earlier calls
-shutil.copy(newest("gpurun_out/%s_kt/*/*kernel_stats.csv" % pre), "profiles/%s/bench_kernel_stats.csv" % rnd)
-shutil.copy("gpurun_out/%s_kt_bench.json" % pre, "profiles/%s/bench_under_rocprof.json" % rnd)
+newest = lambda pat: max(glob.glob(pat), key=os.path.getmtime)       # <outdir> may keep the files of earlier runs
+shutil.copy(newest(src + "/%s_kt/*/*kernel_stats.csv" % pre), "profiles/%s/bench_kernel_stats.csv" % rnd)
+shutil.copy(src + "/%s_kt_bench.json" % pre, "profiles/%s/bench_under_rocprof.json" % rnd)
 try:      # the default command (with the untimed drop-in call: 5 more, shorter launches of the same kernel)
-    shutil.copy(newest("gpurun_out/%s_kte/*/*kernel_stats.csv" % pre), "profiles/%s/bench_kernel_stats_default_command.csv" % rnd)
-    shutil.copy("gpurun_out/%s_kte_bench.json" % pre, "profiles/%s/bench_under_rocprof_default_command.json" % rnd)
+    shutil.copy(newest(src + "/%s_kte/*/*kernel_stats.csv" % pre), "profiles/%s/bench_kernel_stats_default_command.csv" % rnd)
+    shutil.copy(src + "/%s_kte_bench.json" % pre, "profiles/%s/bench_under_rocprof_default_command.json" % rnd)
 except (ValueError, OSError):
     pass
 try:      # config 4
-    shutil.copy(newest("gpurun_out/%s_c4kt/*/*kernel_stats.csv" % pre), "profiles/%s/bench_c4_kernel_stats.csv" % rnd)
-    shutil.copy("gpurun_out/%s_c4kt_bench.json" % pre, "profiles/%s/bench_c4_under_rocprof.json" % rnd)
+    shutil.copy(newest(src + "/%s_c4kt/*/*kernel_stats.csv" % pre), "profiles/%s/bench_c4_kernel_stats.csv" % rnd)
+    shutil.copy(src + "/%s_c4kt_bench.json" % pre, "profiles/%s/bench_c4_under_rocprof.json" % rnd)
 except (ValueError, OSError):
     pass
 KERNEL = "k_horizon<2, false, true, false, false, false>"      # the production instantiation
@@ -29,7 +29,7 @@ LEFT = "k_horizon<2, false, true, false, false, true>"         # its follow-up l
 
 def per_kernel(d, names):
     agg = {}
-    for f in [newest("gpurun_out/%s_%s/*/*counter_collection.csv" % (pre, d))]:
+    for f in [newest(src + "/%s_%s/*/*counter_collection.csv" % (pre, d))]:
         for r in csv.DictReader(open(f)):
             if r["Counter_Name"] in names:
                 agg.setdefault((r["Kernel_Name"].split("(")[0], r["Counter_Name"]), []).append(float(r["Counter_Value"]))
@@ -49,7 +49,7 @@ if kl:      # one follow-up launch per production launch
     f += out["FETCH_SIZE"][kl[0]]["mean_KiB"]; w += out["WRITE_SIZE"][kl[0]]["mean_KiB"]
 cal_r = out["FETCH_SIZE"]["hz::k_bounds"]["mean_KiB"] * 1024 / (12 * 3601 * 3601)
 cal_w = out["WRITE_SIZE"]["hz::k_morton"]["mean_KiB"] * 1024 / (8 * 3600 * 3600)     # key + primitive id per quad
-b = json.loads(open("gpurun_out/%s_kt_bench.json" % pre).read().strip().splitlines()[-1])
+b = json.loads(open(src + "/%s_kt_bench.json" % pre).read().strip().splitlines()[-1])
 t = {"tile": 3601, "azim": 360, "rows_per_step": b["config"]["rows_per_step"], "kernel_asm_sha": sha,
      "device": b["config"].get("device"), "rocm": b["config"].get("rocm"),
      "hbm_bytes_per_launch": 2 * f * 1024 + w * 1024, "fetch_bytes": 2 * f * 1024, "write_bytes": w * 1024,
@@ -70,7 +70,7 @@ if kk:
     m_prod = dict(m)
     for c, v in m_left.items():
         m[c] = m.get(c, 0.0) + v
-    bs = json.loads(open("gpurun_out/%s_sq_bench.json" % pre).read().strip().splitlines()[-1])
+    bs = json.loads(open(src + "/%s_sq_bench.json" % pre).read().strip().splitlines()[-1])
     model_winst = bs["roofline"].get("valu_winst_per_launch")
     d = bs["roofline"].get("valu_model_constants") or dict(bench.VALU_MODEL_DEFAULT)   # the constants that run used
     fac = m["SQ_INSTS_VALU"] / model_winst if model_winst else None
@@ -106,12 +106,12 @@ if kk:
 try:
     agg = {}
     for d in ("c4sq", "c4grbm"):
-        f = newest("gpurun_out/%s_%s/*/*counter_collection.csv" % (pre, d))
+        f = newest(src + "/%s_%s/*/*counter_collection.csv" % (pre, d))
         for r in csv.DictReader(open(f)):
             if "k_shadow" in r["Kernel_Name"]:
                 agg.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
     m = {k: sum(v) / len(v) for k, v in agg.items()}
-    b4 = json.loads(open("gpurun_out/%s_c4kt_bench.json" % pre).read().strip().splitlines()[-1])
+    b4 = json.loads(open(src + "/%s_c4kt_bench.json" % pre).read().strip().splitlines()[-1])
     cyc = m["GRBM_GUI_ACTIVE"] / 8.0
     rf = b4["roofline"]
     out4 = {"kernel": "hz::k_shadow_refill<false>, 144 sun positions per launch", "counters_per_launch": m,
@@ -146,7 +146,7 @@ try:
                       "each kernel and all XCDs", "kernels": {}}
     for d in ("wb1", "wb2", "c4wb1", "c4wb2"):
         try:
-            f = newest("gpurun_out/%s_%s/*/*counter_collection.csv" % (pre, d))
+            f = newest(src + "/%s_%s/*/*counter_collection.csv" % (pre, d))
         except ValueError:
             continue
         for r in csv.DictReader(open(f)):

@@ -20,6 +20,22 @@ def test_bench_needs_a_gpu(gpus):
     assert "needs an MI355X" in (p.stderr + p.stdout) and '"metric"' not in p.stdout
 
 
+def test_plain_run_times_its_steps_only(monkeypatch):
+    """A plain run does what its headline figure needs: every untimed piece that takes runs of its own is off unless --full
+    asks for it, and under --full the --no-* options still drop single pieces."""
+    import bench
+    extra = ("no_count", "no_peaks", "no_extras", "no_e2e", "no_c5_extra", "no_cpu_baseline")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, k) for k in extra) and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not any(getattr(a, k) for k in extra) and (a.steps, a.warmup) == (None, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-c5-extra"])
+    a = bench.parse()
+    assert a.no_c5_extra and not a.no_extras and not a.no_count
+
+
 def test_dump_outputs_layout_and_budget(tmp_path, monkeypatch):
     """--dump-outputs: the SVF of the last step's rows whole while it fits, the horizon at a fixed, seeded sample of cells
     (all azimuths), the (row, column) of every sampled cell; float32 / float64 only, the same files from run to run, and

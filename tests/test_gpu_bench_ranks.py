@@ -49,7 +49,7 @@ def test_plain_bench_gpus_2_starts_two_ranks_and_shards_the_tile(tmp_path):
     shard of the headline tile through dist.sharded_rows and gather the same SVF a single rank computes."""
     np = pytest.importorskip("numpy")
     dump_c5 = str(tmp_path / "c5_two.npy")
-    p, dump2 = _plain(tmp_path, "two", "--c5-tile", "801", "--dump-c5-path", dump_c5, gpus=2)
+    p, dump2 = _plain(tmp_path, "two", "--full", "--c5-tile", "801", "--dump-c5-path", dump_c5, gpus=2)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["steps"] == 2 and d["value"] > 0
@@ -93,7 +93,7 @@ def test_plain_bench_gpus_2_starts_two_ranks_and_shards_the_tile(tmp_path):
     a, b = np.load(dump2), np.load(dump1)
     assert a.shape == (569, 569) and np.isfinite(a).all() and np.array_equal(a, b)
     # ... and the plain N = 1 line (one launch over the whole tile, no process group)
-    r, dump0 = _plain(tmp_path, "plain", "--no-count", "--no-peaks", "--no-c5-extra", gpus=1)
+    r, dump0 = _plain(tmp_path, "plain", "--full", "--no-count", "--no-peaks", "--no-c5-extra", gpus=1)
     assert r.returncode == 0, r.stderr[-3000:]
     d0 = json.loads(r.stdout.strip().splitlines()[-1])
     assert d0["n_gpus"] == 1 and d0["scaling"] == "strong" and d0["config"]["cells_per_step"] == cells
@@ -140,7 +140,7 @@ def test_plain_bench_gpus_4_world_of_four_on_one_gpu(tmp_path):
     ranks (extras.c5, an 801^2 mosaic): four slabs that cover its 769 inner rows and a gathered SVF equal to one rank's."""
     np = pytest.importorskip("numpy")
     dump_c5 = str(tmp_path / "c5_four.npy")
-    p, dump4 = _plain(tmp_path, "four", "--no-count", "--no-peaks", "--c5-tile", "801", "--dump-c5-path", dump_c5, gpus=4)
+    p, dump4 = _plain(tmp_path, "four", "--full", "--no-count", "--no-peaks", "--c5-tile", "801", "--dump-c5-path", dump_c5, gpus=4)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
     c = d["config"]
@@ -228,7 +228,8 @@ def test_config5_single_rank_broadcast_is_free_and_emulated_partition():
 def test_config4_bench_line():
     """bench.py --workload c4 (small tile, 8 sun positions): the shadow line with its own roofline."""
     env = dict(os.environ)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4", "--tile", "601", "--suns", "8", "--steps", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4", "--tile", "601", "--suns", "8", "--steps", "2",
+           "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
