@@ -1877,4 +1877,99 @@ int hz_terrain_destroy(hz_terrain *terrain) {
     return HZ_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// ocean masking (hz_coast.hip): coastline_distance / coastline_buffer, ocean_masking.py:163-345
+// ---------------------------------------------------------------------------------------
+// The largest double T with sqrt_rn(T) <= thr, so that `sqrt(d2) > thr` is `d2 > T` (sqrt_rn is monotone): no square root per
+// cell and the same decisions.  thr < 0: no d2 qualifies (-1); a NaN threshold compares false with everything (+inf: every
+// vertex is "within" it, as `dist > NaN` is false for every cell).
+static double coast_threshold_squared(double thr) {
+    if (thr != thr) return std::numeric_limits<double>::infinity();
+    if (thr < 0.0) return -1.0;
+    if (thr == std::numeric_limits<double>::infinity()) return thr;
+    double t = thr * thr;
+    if (t == std::numeric_limits<double>::infinity()) t = std::numeric_limits<double>::max();
+    for (int k = 0; k < 64 && std::sqrt(t) > thr; k++) t = std::nextafter(t, -1.0);
+    for (int k = 0; k < 64; k++) {
+        const double up = std::nextafter(t, std::numeric_limits<double>::infinity());
+        if (up == std::numeric_limits<double>::infinity() || std::sqrt(up) > thr) break;
+        t = up;
+    }
+    return t;
+}
+
+static int coast_api(int any_hit, const double *x_ecef, const double *y_ecef, const double *z_ecef, const uint8_t *mask_land,
+                     int len_0, int len_1, const double *pts_ecef, size_t num_pts, double dist_thr, double *dist_chord,
+                     uint8_t *mask_buffer, int device, hz_stats *stats) {
+    if (!x_ecef || !y_ecef || !z_ecef || !mask_land || (any_hit ? !mask_buffer : !dist_chord) || (num_pts && !pts_ecef))
+        return set_error(HZ_ERR_ARG, "NULL argument");
+    if (len_0 <= 0 || len_1 <= 0) return set_error(HZ_ERR_ARG, "Input data has inconsistent dimension length(s)");
+    if (num_pts > 0x7fffffffull) return set_error(HZ_ERR_ARG, "too many coastline vertices (%zu; at most 2^31 - 1)", num_pts);
+    int rc = select_device(device);
+    if (rc) return rc;
+    Timer t_total, t;
+    t_total.start();
+    hipStream_t st = nullptr;
+    const size_t n = (size_t)len_0 * len_1;
+    DevIn<double> dx, dy, dz, dp;
+    DevIn<uint8_t> dm;
+    DevOut<double> od;
+    DevOut<uint8_t> ob;
+    t.start();
+    if ((rc = dx.bind(x_ecef, n, st)) || (rc = dy.bind(y_ecef, n, st)) || (rc = dz.bind(z_ecef, n, st)) ||
+        (rc = dm.bind(mask_land, n, st)) || (rc = dp.bind(pts_ecef, num_pts * 3, st)))
+        return rc;
+    if ((rc = any_hit ? ob.bind(mask_buffer, n) : od.bind(dist_chord, n))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    const double t_h2d = t.stop();
+
+    CoastIndex ix;
+    DevScratch scratch;
+    const size_t scratch_bytes = coast_scratch_bytes(num_pts, &ix);
+    HZ_HIP(hipMalloc(&scratch.p, scratch_bytes));
+    t.start();
+    if ((rc = coast_index_build(dp.dev, scratch.p, &ix, st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    const double t_build = t.stop();
+
+    t.start();
+    const double thr2 = any_hit ? coast_threshold_squared(dist_thr) : 0.0;
+    if ((rc = coast_query_launch(ix, dx.dev, dy.dev, dz.dev, dm.dev, len_0, len_1, any_hit, dist_thr, thr2, od.dev, ob.dev, st)))
+        return rc;
+    unsigned long long cnt[HZ_COAST_CNT_N] = {0, 0};
+    HZ_HIP(hipMemcpyAsync(cnt, ix.counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HZ_HIP(hipStreamSynchronize(st));
+    const double t_query = t.stop();
+    if (cnt[1])
+        return set_error(HZ_ERR_BOUND, "%llu cells left the coastline tree's walk at its iteration bound (a defect of the index; "
+                         "no result was written for them)", cnt[1]);
+
+    t.start();
+    if ((rc = any_hit ? ob.finish(st) : od.finish(st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    const double t_d2h = t.stop();
+    if (stats) {
+        *stats = hz_stats();
+        stats->num_cells = cnt[0];
+        stats->t_bvh_s = t_build; stats->t_kernel_s = t_query; stats->t_h2d_s = t_h2d; stats->t_d2h_s = t_d2h;
+        stats->t_total_s = t_total.stop();
+        stats->scratch_bytes = scratch_bytes;
+    }
+    return HZ_OK;
+}
+
+int hz_coastline_distance(const double *x_ecef, const double *y_ecef, const double *z_ecef, const uint8_t *mask_land,
+                          int len_0, int len_1, const double *pts_ecef, size_t num_pts, double *dist_chord, int device,
+                          hz_stats *stats) {
+    return coast_api(0, x_ecef, y_ecef, z_ecef, mask_land, len_0, len_1, pts_ecef, num_pts, 0.0, dist_chord, nullptr, device,
+                     stats);
+}
+
+int hz_coastline_buffer(const double *x_ecef, const double *y_ecef, const double *z_ecef, const uint8_t *mask_land,
+                        int len_0, int len_1, const double *pts_ecef, size_t num_pts, double dist_thr, uint8_t *mask_buffer,
+                        int device, hz_stats *stats) {
+    return coast_api(1, x_ecef, y_ecef, z_ecef, mask_land, len_0, len_1, pts_ecef, num_pts, dist_thr, nullptr, mask_buffer,
+                     device, stats);
+}
+
 }  // extern "C"

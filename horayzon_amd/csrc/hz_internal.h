@@ -244,6 +244,25 @@ int radix_sort_pairs_u32(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, u
                          uint32_t *temp, hipStream_t st, int passes = 4);
 int exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *temp, hipStream_t st);
 
+// hz_coast.hip: nearest coastline vertex of every water cell (float64)
+#define HZ_COAST_LEAF 8                  // sorted vertices per leaf
+#define HZ_COAST_CNT_N 2                 // u64 counters: [0] water cells queried, [1] lanes that hit the iteration bound
+struct CoastIndex {
+    uint32_t n_pts = 0, n_leaf = 0, n_leaf_pad = 1;
+    size_t off_counters = 0, off_sorted = 0, off_nodes = 0, off_bbox = 0, off_sort = 0;   // layout of the scratch block
+    unsigned long long *counters = nullptr;
+    const double *sorted = nullptr;      // f64[n_leaf * HZ_COAST_LEAF][3], Morton order
+    const void *nodes = nullptr;         // heap-ordered boxes, 2 * n_leaf_pad of 48 bytes
+};
+// bytes of device scratch the index of num_pts vertices needs (fills the sizes and offsets of *ix)
+size_t coast_scratch_bytes(size_t num_pts, CoastIndex *ix);
+int coast_index_build(const double *pts, void *scratch, CoastIndex *ix, hipStream_t st);
+// any_hit = 0: dist f64[len_0][len_1]; 1: mask_buffer u8[len_0][len_1] = (distance > thr), thr2 = the largest double whose
+// correctly rounded square root is <= thr.  All pointers device memory.
+int coast_query_launch(const CoastIndex &ix, const double *x, const double *y, const double *z, const uint8_t *mask_land,
+                       int len_0, int len_1, int any_hit, double thr, double thr2, double *dist, uint8_t *mask_buffer,
+                       hipStream_t st);
+
 // hz_bench.hip: machine calibration kernels (current device)
 int bench_valu_peak(int packed, int waves_per_simd, double *winst_per_s_per_simd, double *clock_ghz, int *simds);
 int bench_copy_peak(size_t bytes, double *gbs);

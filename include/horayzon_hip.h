@@ -34,6 +34,7 @@ extern "C" {
 #define HZ_ERR_HIP 2      /* HIP runtime failure (message has the HIP error)   */
 #define HZ_ERR_NODEV 3    /* no usable gfx950 device                           */
 #define HZ_ERR_DEPTH 4    /* BVH deeper than the traversal stack               */
+#define HZ_ERR_BOUND 5    /* a bounded device loop reached its iteration limit */
 
 /* Optional controls; pass NULL for the reference's behaviour on device 0.     */
 typedef struct hz_opts {
@@ -399,6 +400,30 @@ int hz_terrain_accumulate(hz_terrain *terrain, const float *sun_positions, const
 int hz_terrain_count_work(hz_terrain *terrain, int on);
 /* CppTerrain::~CppTerrain, shadow_comp.cpp:310-316 */
 int hz_terrain_destroy(hz_terrain *terrain);
+
+/* ------------------------------------------------------------------------- */
+/* Ocean masking: the `mask` argument of the entry points above, from a land-sea mask and the coastline        */
+/* ------------------------------------------------------------------------- */
+/* Contract, all float64, every operation rounded once: for a water cell c (mask_land[c] == 0) and a vertex p    */
+/*   d2(c, p) = ((cx - px) * (cx - px) + (cy - py) * (cy - py)) + (cz - pz) * (cz - pz)                         */
+/*   dist_chord[c] = sqrt(min over p of d2(c, p)), correctly rounded; land cells NaN; num_pts == 0: +inf         */
+/*   mask_buffer[c] = dist_chord[c] > dist_thr; land cells 0                                                    */
+/* x_ecef, y_ecef, z_ecef f64[len_0][len_1] [m], mask_land u8[len_0][len_1] (0 = water), pts_ecef                */
+/* f64[num_pts][3] [m] (num_pts < 2^31; NULL allowed when 0); host or device pointers.  The vertices are indexed  */
+/* on the device in every call (Morton sort, boxes over leaves of 8); the results do not depend on the index.   */
+/* stats (may be NULL): t_bvh_s index build, t_kernel_s query, t_h2d_s, t_d2h_s, t_total_s, num_cells = water    */
+/* cells queried, scratch_bytes = device memory of the index and its build.                                     */
+/* coastline_distance, ocean_masking.py:163-212 (the k-d tree query for every water cell)                       */
+int hz_coastline_distance(const double *x_ecef, const double *y_ecef, const double *z_ecef,
+                          const uint8_t *mask_land, int len_0, int len_1,
+                          const double *pts_ecef, size_t num_pts,
+                          double *dist_chord, int device, hz_stats *stats);
+/* coastline_buffer, ocean_masking.py:217-345, without its block pre-classification: every water cell is decided  */
+/* exactly, by an any-hit query that ends at the first vertex within dist_thr                                    */
+int hz_coastline_buffer(const double *x_ecef, const double *y_ecef, const double *z_ecef,
+                        const uint8_t *mask_land, int len_0, int len_1,
+                        const double *pts_ecef, size_t num_pts, double dist_thr,
+                        uint8_t *mask_buffer, int device, hz_stats *stats);
 
 #ifdef __cplusplus
 }
