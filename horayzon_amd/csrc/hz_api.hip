@@ -1273,7 +1273,8 @@ int hz_horizon_tables(int azim_num, float hori_acc, float elev_ang_low_lim, floa
 static int topo_api(int kind, const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
                     int len_2, float *out, int device) {
     if (!azim || !hori || !out || (kind != 2 && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
-    if (len_0 <= 0 || len_1 <= 0 || len_2 < 2) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
+    // (the openness reads no azim[1] - azim[0]: one azimuth is enough, as in hz_topo_params and the reference)
+    if (len_0 <= 0 || len_1 <= 0 || len_2 < (kind == 2 ? 1 : 2)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
     int rc = select_device(device);
     if (rc) return rc;
     hipStream_t st = nullptr;

@@ -741,8 +741,10 @@ int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *u
 // double-angle formulas, |error| < 2e-7; every multiply and add rounds separately, -ffp-contract=off).  With the float64 pair of
 // rounds 3 - 5 the kernel was bound by its float64 instructions (7.8e9 wave instructions at 4 cycles = 12.7 ms for 18.35 GB:
 // 1.6 TB/s), not by memory.  What decides the result's accuracy is the float32 accumulator both sides share (half an ulp of a sum
-// of ~100: 4e-6 per add before the division by azim_num), not the 1e-7 of a term: against the reference-made fixtures the float32
-// terms differ by <= 2.4e-7 (tests/test_gpu_prep.py; the bar is 1e-5, the reference itself is built with -ffast-math), and
+// of ~100: 4e-6 per add before the division by azim_num), not the 1e-7 of a term: against a float64 evaluation of the same
+// formulas the result is off by no more than the reference's own error E_ref plus 2.4e-7 (measured: E_ref + 1.2e-7 at most, over
+// 2 ... 3456 azimuths, slopes up to 89.5 degrees, horizons -30 ... 85 degrees and +-pi/2: tests/test_gpu_topo_reference.py,
+// DESIGN.md section 5; the older bar against the reference-made fixtures is 1e-5), and
 // k_topo_wide keeps libm's float64 routines per azimuth as the Cython code has them.  Each lane prefetches its share of the next
 // block into registers before it reduces the current one.
 // ---------------------------------------------------------------------------------------
@@ -843,8 +845,11 @@ __global__ __launch_bounds__(256, HZ_TOPO_WG) void k_topo(const float *__restric
                 // sine and cosine of the plane's horizon come from its tangent: cos = 1 / sqrt(1 + x^2), sin = x cos
                 if (!(hv >= hp)) {
                     he = hp;
-                    const float rc = __builtin_amdgcn_rsqf(1.0f + xf * xf);
-                    cs = rc; sn = xf * rc;
+                    // (xf * xf overflows for a plane that stands upright, tz == 0: rc is 0 and xf * rc would be inf * 0;
+                    //  the reference takes the sine of atan(+-inf) = +-pi/2 there)
+                    const float x2 = 1.0f + xf * xf;
+                    const float rc = __builtin_amdgcn_rsqf(x2);
+                    cs = rc; sn = (x2 == INFINITY) ? copysignf(1.0f, xf) : xf * rc;
                 }
             }
             if (KIND == 0) {
@@ -972,8 +977,9 @@ __global__ __launch_bounds__(256, HZ_TOPO_WG) void k_topo_multi(const float *__r
                 const float hp = atanf(xf);
                 if (!(hv >= hp)) {
                     he = hp;
-                    const float rc = __builtin_amdgcn_rsqf(1.0f + xf * xf);
-                    cs = rc; sn = xf * rc;
+                    const float x2 = 1.0f + xf * xf;                                  // as k_topo: an upright plane
+                    const float rc = __builtin_amdgcn_rsqf(x2);
+                    cs = rc; sn = (x2 == INFINITY) ? copysignf(1.0f, xf) : xf * rc;
                 }
             }
             if (WANT & HZ_TOPO_SVF) agg_svf = agg_svf + ((tx * as + ty * ac) * ((half_pi_f - he) - sn * cs) + tz * (cs * cs));
