@@ -1383,6 +1383,7 @@ int hz_debug_set(const char *key, int value) {
     if (!strcmp(key, "shadow_fast_cap")) hz::g_shadow_fast_cap.store(value < 0 ? HZ_SHADOW_FAST_CAP_DEFAULT : value, std::memory_order_relaxed);
     else if (!strcmp(key, "topo_wide")) hz::g_topo_wide.store(value != 0, std::memory_order_relaxed);
     else if (!strcmp(key, "accum_chunk")) hz::g_accum_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "coarse_tile")) hz::g_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
 }
@@ -1845,6 +1846,100 @@ int hz_terrain_accumulate(hz_terrain *terrain, const float *sun_positions, const
             if ((rc = accum_add_launch(a.out_u8, a.out_f32, nc, kc, w, acc_sw, acc_lit, st))) return rc;
         }
         if ((rc = accum_final_launch(a.mask, nc, t->fill, acc_sw, acc_lit, d_sw.dev, d_lit.dev, st))) return rc;
+        HZ_HIP(hipEventRecord(e1, st));
+        HZ_HIP(hipEventSynchronize(e1));
+        HZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+        HZ_HIP(hipMemcpyAsync(cnt, t->counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HZ_HIP(hipStreamSynchronize(st));
+    }
+    Timer t_d2h; t_d2h.start();
+    if ((rc = d_sw.finish(st))) return rc;
+    if ((rc = d_lit.finish(st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    if (stats) {
+        stats->num_rays += cnt[0];
+        stats->nodes_visited += cnt[1]; stats->tris_tested += cnt[2];
+        stats->wave_node_iters += cnt[3]; stats->wave_leaf_iters += cnt[4];
+        stats->t_kernel_s += (double)ms * 1e-3;
+        stats->t_d2h_s += t_d2h.stop();
+        stats->t_total_s += t_total.stop();
+        stats->bvh_height = t->scene->hdr.height; stats->scene_bytes = t->scene->hdr.total_bytes;
+        stats->scratch_bytes = scratch;
+    }
+    return HZ_OK;
+}
+
+// Terrain.sw_dir_cor_coarse (hz_subgrid.hip: k_coarse_count, k_coarse_reduce).  accumulate's chunks and scratch; instead of
+// per-cell accumulators every chunk is reduced over blocks of pixel_per_gc_0 x pixel_per_gc_1 cells straight into the
+// outputs at its first position.  Device memory besides the outputs -- scratch, the cell counts of the coarse cells, staged
+// positions -- does not depend on num_sun (outputs given as host pointers are staged on the device: num_sun * gy * gx floats).
+int hz_terrain_sw_dir_cor_coarse(hz_terrain *terrain, const float *sun_positions, int num_sun, int pixel_per_gc_0,
+                                 int pixel_per_gc_1, float *f_cor, float *sunlit_frac, hz_stats *stats) {
+    Terrain *t = reinterpret_cast<Terrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "Terrain is not initialised");
+    if (!sun_positions || num_sun <= 0) return set_error(HZ_ERR_ARG, "array 'sun_positions' has incorrect shape");
+    if (!f_cor && !sunlit_frac) return set_error(HZ_ERR_ARG, "no output buffer (f_cor and sunlit_frac are NULL)");
+    if (f_cor == sunlit_frac) return set_error(HZ_ERR_ARG, "'f_cor' and 'sunlit_frac' must be different arrays");
+    const int p0 = pixel_per_gc_0, p1 = pixel_per_gc_1;
+    if (p0 < 1 || p1 < 1 || p0 > t->dim_in_0 || p1 > t->dim_in_1 || t->dim_in_0 % p0 || t->dim_in_1 % p1)
+        return set_error(HZ_ERR_ARG, "'pixel_per_gc' (%d, %d) must be positive and divide the inner domain (%d, %d)", p0, p1,
+                         t->dim_in_0, t->dim_in_1);
+    HZ_HIP(hipSetDevice(t->device));
+    std::lock_guard<std::mutex> run_lock(t->scene->run_mu);
+    hipStream_t st = t->stream;
+    Timer t_total; t_total.start();
+    const size_t nc = (size_t)t->dim_in_0 * t->dim_in_1;
+    const int gy = t->dim_in_0 / p0, gx = t->dim_in_1 / p1;
+    const size_t ng = (size_t)gy * gx;
+    const bool want_sw = f_cor != nullptr, want_lit = sunlit_frac != nullptr;
+    // the sunlit fraction needs the shadow code (which = 0: the shadow ray set); the correction alone traces its own, smaller set
+    ShadowArgs a = terrain_args(t, want_lit ? 0 : 1);
+    int k = g_accum_chunk.load(std::memory_order_relaxed);       // (hz_debug_set("accum_chunk", k): tests)
+    if (k <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HZ_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t budget = std::min<size_t>(HZ_ACCUM_BUDGET, free_b / 4);
+        const size_t per_pos = nc * ((want_lit ? 1 : 0) + (want_sw ? 4 : 0));
+        k = (int)std::max<size_t>(1, std::min<size_t>(HZ_ACCUM_CHUNK_MAX, budget / per_pos));
+    }
+    k = std::min(k, 32768);                                       // grid.y of one launch
+    const bool sun_on_dev = is_device_ptr(sun_positions);
+    DevScratch codes, vals, count, stage;
+    size_t scratch = 0;
+    if (want_lit) { HZ_HIP(hipMalloc(&codes.p, (size_t)k * nc)); scratch += (size_t)k * nc; }
+    if (want_sw) { HZ_HIP(hipMalloc(&vals.p, (size_t)k * nc * 4)); scratch += (size_t)k * nc * 4; }
+    HZ_HIP(hipMalloc(&count.p, ng * sizeof(unsigned))); scratch += ng * sizeof(unsigned);
+    if (!sun_on_dev) { HZ_HIP(hipMalloc(&stage.p, (size_t)k * 3 * sizeof(float))); scratch += (size_t)k * 3 * sizeof(float); }
+    float *stage_sun = static_cast<float *>(stage.p);           // host positions go up one chunk at a time
+    DevOut<float> d_sw, d_lit;
+    int rc;
+    if ((rc = d_sw.bind(f_cor, want_sw ? ng * (size_t)num_sun : 0))) return rc;
+    if ((rc = d_lit.bind(sunlit_frac, want_lit ? ng * (size_t)num_sun : 0))) return rc;
+    float ms = 0.0f;
+    unsigned long long cnt[16];
+    {
+        HZ_HIP(hipMemsetAsync(t->counters, 0, 16 * sizeof(unsigned long long), st));
+        hipEvent_t e0, e1;
+        HZ_HIP(hipEventCreate(&e0)); HZ_HIP(hipEventCreate(&e1));
+        struct EvFree { hipEvent_t a, b; ~EvFree() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_free{e0, e1};
+        HZ_HIP(hipEventRecord(e0, st));
+        if ((rc = coarse_count_launch(a.mask, t->dim_in_0, t->dim_in_1, p0, p1, static_cast<unsigned *>(count.p), st))) return rc;
+        a.out_u8 = static_cast<uint8_t *>(codes.p);
+        a.out_f32 = static_cast<float *>(vals.p);
+        for (int s0 = 0; s0 < num_sun; s0 += k) {
+            const int kc = std::min(k, num_sun - s0);
+            if (sun_on_dev) a.suns = sun_positions + 3 * (size_t)s0;
+            else {
+                HZ_HIP(hipMemcpyAsync(stage_sun, sun_positions + 3 * (size_t)s0, (size_t)kc * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+                a.suns = stage_sun;
+            }
+            a.num_sun = kc;
+            if ((rc = accum_trace_launch(t->scene, a, want_sw && want_lit, st))) return rc;
+            if ((rc = coarse_reduce_launch(a.out_u8, a.out_f32, a.mask, static_cast<const unsigned *>(count.p), t->dim_in_0,
+                                           t->dim_in_1, p0, p1, kc, t->fill, d_sw.dev ? d_sw.dev + ng * (size_t)s0 : nullptr,
+                                           d_lit.dev ? d_lit.dev + ng * (size_t)s0 : nullptr, st)))
+                return rc;
+        }
         HZ_HIP(hipEventRecord(e1, st));
         HZ_HIP(hipEventSynchronize(e1));
         HZ_HIP(hipEventElapsedTime(&ms, e0, e1));

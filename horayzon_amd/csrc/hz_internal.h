@@ -29,6 +29,7 @@ int set_error(int code, const char *fmt, ...);
 extern std::atomic<int> g_shadow_fast_cap;   // entries of k_shadow_refill's fast stack (default HZ_SHADOW_FAST_CAP_DEFAULT; 0: level stack only)
 extern std::atomic<int> g_topo_wide;         // 1: the reductions over the azimuth axis use the fallback kernel k_topo_wide
 extern std::atomic<int> g_accum_chunk;       // > 0: sun positions per chunk of hz_terrain_accumulate (default 0: from the memory budget)
+extern std::atomic<int> g_coarse_tile;       // > 0: cells of k_coarse_reduce's LDS tile, at most the default (hz_subgrid.hip; default 0)
 
 #define HZ_HIP(expr)                                                                      \
     do {                                                                                  \
@@ -236,6 +237,13 @@ int accum_add_launch(const uint8_t *codes, const float *vals, size_t n, int k, c
                      hipStream_t st);
 int accum_final_launch(const uint8_t *mask, size_t n, float fill, const double *acc_sw, const double *acc_lit, float *out_sw,
                        float *out_lit, hipStream_t st);
+
+// hz_subgrid.hip (hz_terrain_sw_dir_cor_coarse; device pointers): n u32[dim_0 / p0][dim_1 / p1] = unmasked cells per coarse
+// cell; one chunk of k positions of accumulate's scratch (codes and / or vals, [k][cells]) reduced to block means
+// f_cor / lit f32[k][gy][gx] (null: not wanted; f_cor needs vals, lit needs codes), coarse cells without a cell = fill
+int coarse_count_launch(const uint8_t *mask, int dim_0, int dim_1, int p0, int p1, unsigned *n, hipStream_t st);
+int coarse_reduce_launch(const uint8_t *codes, const float *vals, const uint8_t *mask, const unsigned *n, int dim_0, int dim_1,
+                         int p0, int p1, int k, float fill, float *f_cor, float *lit, hipStream_t st);
 
 // hz_sort.hip: hand-written stable LSD radix sort (pairs) and exclusive scan, uint32
 size_t sort_temp_elems(size_t n);

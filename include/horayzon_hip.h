@@ -302,7 +302,9 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* test knobs (process wide; results never depend on them): "shadow_fast_cap" = entries of the shadow kernel's fast stack (< 0: */
 /* the default; small values make the in-kernel retry with the level stack the common case), "topo_wide" = 1: the reductions    */
 /* over the azimuth axis use the one-lane-per-cell fallback kernel, "accum_chunk" = sun positions per chunk of                   */
-/* hz_terrain_accumulate (<= 0: the default, from the scratch budget)                                                           */
+/* hz_terrain_accumulate and hz_terrain_sw_dir_cor_coarse (<= 0: the default, from the scratch budget), "coarse_tile" = cells   */
+/* of the LDS tile of hz_terrain_sw_dir_cor_coarse's reduction (<= 0 or above the default: the default; blocks wider than the  */
+/* tile take the kernel without LDS)                                                                                            */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */
@@ -395,6 +397,23 @@ int hz_terrain_sw_dir_cor_batch(hz_terrain *terrain, const float *sun_positions,
 /* with dot_ts > dot_prod_min; device scratch (hz_stats.scratch_bytes) does not grow with num_sun  */
 int hz_terrain_accumulate(hz_terrain *terrain, const float *sun_positions, const float *weights, int num_sun,
                           float *sw_dir_cor_sum, float *sunlit_sum, hz_stats *stats);
+/* additive: per sun position, means over blocks of pixel_per_gc_0 x pixel_per_gc_1 cells of the inner domain (each >= 1 and  */
+/* a divisor of dim_in_0 / dim_in_1; gy = dim_in_0 / pixel_per_gc_0, gx = dim_in_1 / pixel_per_gc_1), without a map per        */
+/* position. For position s and coarse cell (I, J), B = the cells (i, j), I * P0 <= i < (I + 1) * P0, J * P1 <= j < (J + 1)    */
+/* * P1, with mask[i][j] == 1, and n = |B|:                                                                                     */
+/*   f_cor[s][I][J] = (float)(SUM / (double)n), SUM a float64 accumulator that starts at 0.0 and takes                          */
+/*     (double)sw_dir_cor_s[i][j] -- bit for bit what hz_terrain_sw_dir_cor writes for position s -- one cell at a time over B, */
+/*     i ascending and within a row j ascending (the order is part of the contract: a float64 sum of float32 values is not      */
+/*     exact in general; the library is built with -ffp-contract=off);                                                          */
+/*   sunlit_frac[s][I][J] = (float)((double)n_lit / (double)n), n_lit = the cells of B for which hz_terrain_shadow gives 0;    */
+/*   n == 0: both are sw_dir_cor_fill.                                                                                          */
+/* f_cor, sunlit_frac f32[num_sun][gy][gx]; NULL = not wanted (at least one; they must differ). Positions and outputs may be    */
+/* host or device pointers. Rays as in hz_terrain_accumulate: one per (cell, position) with dot_ts > 0 if sunlit_frac is        */
+/* wanted (it serves both outputs), else with dot_ts > dot_prod_min; device memory besides the outputs                          */
+/* (hz_stats.scratch_bytes) does not grow with num_sun                                                                          */
+int hz_terrain_sw_dir_cor_coarse(hz_terrain *terrain, const float *sun_positions, int num_sun,
+                                 int pixel_per_gc_0, int pixel_per_gc_1,
+                                 float *f_cor, float *sunlit_frac, hz_stats *stats);
 /* additive: 1 = later shadow / sw_dir_cor calls run the counting instantiation and also fill   */
 /* hz_stats.nodes_visited / tris_tested / wave_*_iters (slower; for the roofline's B_trav)      */
 int hz_terrain_count_work(hz_terrain *terrain, int on);
