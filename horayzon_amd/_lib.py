@@ -60,6 +60,15 @@ class hz_topo_out(C.Structure):
         super().__init__(C.sizeof(hz_topo_out), vsf, openness)
 
 
+class hz_horisun_out(C.Structure):
+    """Outputs of hz_horizon_terrain_run (None: not wanted); `size` is set to sizeof(hz_horisun_out)."""
+    _fields_ = [("size", C.c_int32), ("shadow", C.c_void_p), ("sw_dir_cor", C.c_void_p),
+                ("sw_dir_cor_sum", C.c_void_p), ("sunlit_sum", C.c_void_p)]
+
+    def __init__(self, shadow=None, sw_dir_cor=None, sw_dir_cor_sum=None, sunlit_sum=None):
+        super().__init__(C.sizeof(hz_horisun_out), shadow, sw_dir_cor, sw_dir_cor_sum, sunlit_sum)
+
+
 # every symbol include/horayzon_hip.h declares (tests check that all are exported)
 SYMBOLS = (
     "hz_last_error", "hz_abi_struct_sizes", "hz_abi_version", "hz_device_count", "hz_device_info",
@@ -77,6 +86,7 @@ SYMBOLS = (
     "hz_terrain_sw_dir_cor_batch", "hz_terrain_count_work", "hz_terrain_destroy",
     "hz_terrain_accumulate", "hz_terrain_sw_dir_cor_coarse",
     "hz_coastline_distance", "hz_coastline_buffer",
+    "hz_horizon_terrain_create", "hz_horizon_terrain_initialise", "hz_horizon_terrain_run", "hz_horizon_terrain_destroy",
 )
 
 
@@ -178,6 +188,11 @@ def lib():
     L.hz_coastline_distance.argtypes = [vp, vp, vp, vp, ip, ip, vp, C.c_size_t, vp, ip, C.POINTER(hz_stats)]
     L.hz_coastline_buffer.argtypes = [vp, vp, vp, vp, ip, ip, vp, C.c_size_t, C.c_double, vp, ip, C.POINTER(hz_stats)]
     L.hz_terrain_destroy.argtypes = [vp]
+    L.hz_horizon_terrain_create.argtypes = [ip, C.POINTER(vp)]
+    L.hz_horizon_terrain_initialise.argtypes = [vp, vp, ip, vp, ip, ip, ip, ip, vp, vp, vp, ip, ip, vp, vp,
+                                                C.c_float, C.c_float, C.POINTER(hz_stats)]
+    L.hz_horizon_terrain_run.argtypes = [vp, vp, vp, ip, C.POINTER(hz_horisun_out), C.POINTER(hz_stats)]
+    L.hz_horizon_terrain_destroy.argtypes = [vp]
     for name in SYMBOLS:
         if name not in ("hz_last_error", "hz_vert_grid_len"):
             getattr(L, name).restype = C.c_int

@@ -4,6 +4,7 @@
 // and CppTerrain (shadow_comp.cpp:304-605): unit conversions, trig tables with the
 // reference's float/double promotion pattern, uploads, kernel launches, reports.
 #include "hz_internal.h"
+#include "hz_horisun_plan.h"
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -1384,6 +1385,7 @@ int hz_debug_set(const char *key, int value) {
     else if (!strcmp(key, "topo_wide")) hz::g_topo_wide.store(value != 0, std::memory_order_relaxed);
     else if (!strcmp(key, "accum_chunk")) hz::g_accum_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "coarse_tile")) hz::g_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "horisun_chunk")) hz::g_horisun_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
 }
@@ -1969,6 +1971,218 @@ int hz_terrain_destroy(hz_terrain *terrain) {
     (void)hipSetDevice(t->device);
     terrain_release_arrays(t);
     if (t->counters) (void)hipFree(t->counters);
+    delete t;
+    return HZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// HorizonTerrain (hz_horisun.hip): Terrain's answers from a stored horizon, DESIGN.md section 4 clause 10
+// ---------------------------------------------------------------------------------------
+struct HorizonTerrain {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::mutex run_mu;                        // calls on one handle run one after the other (they share the stream)
+    const float *hori = nullptr;              // device; borrowed when the caller gave a device pointer
+    bool own_hori = false;
+    int azim_num = 0, dim_in_0 = 0, dim_in_1 = 0;
+    void *vert = nullptr, *tilt = nullptr, *norm = nullptr, *north = nullptr, *enl = nullptr, *mask = nullptr;   // owned copies
+    float fill = 0, ang_max = 89.0f;
+    bool initialised = false;
+};
+
+static void horisun_release(HorizonTerrain *t) {
+    (void)hipSetDevice(t->device);
+    if (t->stream) (void)hipStreamSynchronize(t->stream);
+    if (t->own_hori && t->hori) (void)hipFree(const_cast<float *>(t->hori));
+    for (void **q : {&t->vert, &t->tilt, &t->norm, &t->north, &t->enl, &t->mask}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    t->hori = nullptr; t->own_hori = false; t->initialised = false;
+}
+
+// device copy of `bytes` bytes of host or device memory (the object keeps no pointer of the caller's besides a device `hori`)
+static int horisun_copy(const void *src, size_t bytes, hipStream_t st, void **dst) {
+    HZ_HIP(hipMalloc(dst, bytes ? bytes : 16));
+    HZ_HIP(hipMemcpyAsync(*dst, src, bytes, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    return HZ_OK;
+}
+
+int hz_horizon_terrain_create(int device, hz_horizon_terrain **terrain) {
+    if (!terrain) return set_error(HZ_ERR_ARG, "terrain is NULL");
+    int rc = select_device(device);
+    if (rc) return rc;
+    HorizonTerrain *t = new HorizonTerrain();
+    t->device = device;
+    if ((rc = stream_acquire(device, &t->stream))) { delete t; return rc; }
+    *terrain = reinterpret_cast<hz_horizon_terrain *>(t);
+    return HZ_OK;
+}
+
+int hz_horizon_terrain_initialise(hz_horizon_terrain *terrain, const float *hori, int azim_num, const float *vert_grid,
+                                  int dem_dim_0, int dem_dim_1, int offset_0, int offset_1, const float *vec_tilt,
+                                  const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
+                                  const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
+                                  hz_stats *stats) {
+    HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
+    if (!t) return set_error(HZ_ERR_ARG, "terrain is NULL");
+    if (!hori || !vert_grid || !vec_tilt || !vec_norm || !vec_north || !surf_enl_fac || !mask)
+        return set_error(HZ_ERR_ARG, "NULL input array");
+    if (azim_num < 1) return set_error(HZ_ERR_ARG, "'azim_num' must be at least 1");
+    if (dim_in_0 <= 0 || dim_in_1 <= 0 || offset_0 < 0 || offset_1 < 0 || dem_dim_0 <= 0 || dem_dim_1 <= 0 ||
+        (long long)offset_0 + dim_in_0 > dem_dim_0 || (long long)offset_1 + dim_in_1 > dem_dim_1)
+        return set_error(HZ_ERR_ARG, "inconsistency between input arguments 'dem_dim_0', 'dem_dim_1', 'offset_0', 'offset_1' and 'vec_norm'");
+    if (!(ang_max >= 85.0f && ang_max <= 89.99f)) return set_error(HZ_ERR_ARG, "'ang_max' must be in the range [85.0, 89.99]");
+    HorisunPlan plan;
+    if (horisun_plan(dim_in_0, dim_in_1, azim_num, 1, 0, 0, &plan)) return set_error(HZ_ERR_ARG, "the inner domain or 'hori' is too large");
+    std::lock_guard<std::mutex> run_lock(t->run_mu);
+    horisun_release(t);
+    HZ_HIP(hipSetDevice(t->device));
+    hipStream_t st = t->stream;
+    Timer t_total; t_total.start();
+    const size_t nc = plan.cells;
+    int rc = HZ_OK;
+    if (is_device_ptr(hori)) { t->hori = hori; t->own_hori = false; }
+    else {
+        void *h = nullptr;
+        rc = horisun_copy(hori, nc * (size_t)azim_num * sizeof(float), st, &h);
+        t->hori = static_cast<const float *>(h); t->own_hori = true;
+    }
+    if (!rc) rc = horisun_copy(vec_tilt, nc * 12, st, &t->tilt);
+    if (!rc) rc = horisun_copy(vec_norm, nc * 12, st, &t->norm);
+    if (!rc) rc = horisun_copy(vec_north, nc * 12, st, &t->north);
+    if (!rc) rc = horisun_copy(surf_enl_fac, nc * 4, st, &t->enl);
+    if (!rc) rc = horisun_copy(mask, nc, st, &t->mask);
+    // the vertices of the inner domain only: rows of dim_in_1 vertices out of DEM rows of dem_dim_1
+    if (!rc) {
+        const hipError_t e = hipMalloc(&t->vert, nc * 12);
+        if (e != hipSuccess) rc = set_error(HZ_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) {
+        const float *src = vert_grid + 3 * ((size_t)offset_0 * (size_t)dem_dim_1 + (size_t)offset_1);
+        const hipError_t e = hipMemcpy2DAsync(t->vert, (size_t)dim_in_1 * 12, src, (size_t)dem_dim_1 * 12, (size_t)dim_in_1 * 12,
+                                              (size_t)dim_in_0, is_device_ptr(vert_grid) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) rc = set_error(HZ_ERR_HIP, "hipMemcpy2DAsync failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) {
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = set_error(HZ_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    if (rc) { horisun_release(t); return rc; }
+    t->azim_num = azim_num; t->dim_in_0 = dim_in_0; t->dim_in_1 = dim_in_1;
+    t->fill = sw_dir_cor_fill; t->ang_max = ang_max;
+    t->initialised = true;
+    if (stats) {
+        const double dt = t_total.stop();
+        stats->t_h2d_s += dt; stats->t_total_s += dt;
+        stats->num_cells = nc;
+    }
+    return HZ_OK;
+}
+
+int hz_horizon_terrain_run(hz_horizon_terrain *terrain, const float *sun_positions, const float *weights, int num_sun,
+                           const hz_horisun_out *out, hz_stats *stats) {
+    HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "HorizonTerrain is not initialised");
+    if (!sun_positions || num_sun <= 0) return set_error(HZ_ERR_ARG, "array 'sun_positions' has incorrect shape");
+    if (!out || out->size != (int32_t)sizeof(hz_horisun_out))
+        return set_error(HZ_ERR_ARG, "hz_horisun_out.size is %d, expected %d", out ? (int)out->size : 0, (int)sizeof(hz_horisun_out));
+    const void *outs[4] = {out->shadow, out->sw_dir_cor, out->sw_dir_cor_sum, out->sunlit_sum};
+    if (!outs[0] && !outs[1] && !outs[2] && !outs[3]) return set_error(HZ_ERR_ARG, "no output buffer (every pointer of hz_horisun_out is NULL)");
+    for (int i = 0; i < 4; i++)
+        for (int j = i + 1; j < 4; j++)
+            if (outs[i] && outs[i] == outs[j]) return set_error(HZ_ERR_ARG, "the outputs must be different arrays");
+    const bool want_sums = out->sw_dir_cor_sum || out->sunlit_sum;
+    HorisunPlan plan;
+    if (horisun_plan(t->dim_in_0, t->dim_in_1, t->azim_num, num_sun, g_horisun_chunk.load(std::memory_order_relaxed),
+                     (out->shadow ? 1 : 0) + (out->sw_dir_cor ? 4 : 0), &plan))
+        return set_error(HZ_ERR_ARG, "too many sun positions for the per-position outputs");
+    std::lock_guard<std::mutex> run_lock(t->run_mu);
+    HZ_HIP(hipSetDevice(t->device));
+    hipStream_t st = t->stream;
+    Timer t_total; t_total.start();
+    const size_t nc = plan.cells;
+    const int k = plan.chunk;
+    const bool sun_on_dev = is_device_ptr(sun_positions);
+    const bool use_w = weights && want_sums, w_on_dev = use_w && is_device_ptr(weights);
+    DevScratch acc, stage;
+    size_t scratch = 0;
+    // the sums live in registers during a launch and in two float64 maps between the launches of a call
+    const size_t n_acc = (out->sw_dir_cor_sum ? 1 : 0) + (out->sunlit_sum ? 1 : 0);
+    if (n_acc) { HZ_HIP(hipMalloc(&acc.p, n_acc * nc * sizeof(double))); scratch += n_acc * nc * sizeof(double); }
+    float *stage_sun = nullptr, *stage_w = nullptr;              // host positions / weights go up one chunk at a time
+    if (!sun_on_dev || (use_w && !w_on_dev)) {
+        HZ_HIP(hipMalloc(&stage.p, (size_t)k * 4 * sizeof(float))); scratch += (size_t)k * 4 * sizeof(float);
+        stage_sun = static_cast<float *>(stage.p); stage_w = stage_sun + 3 * (size_t)k;
+    }
+    DevOut<uint8_t> d_u8; DevOut<float> d_f32, d_sw, d_lit;
+    int rc;
+    if ((rc = d_u8.bind(out->shadow, out->shadow ? nc * (size_t)num_sun : 0))) return rc;
+    if ((rc = d_f32.bind(out->sw_dir_cor, out->sw_dir_cor ? nc * (size_t)num_sun : 0))) return rc;
+    if ((rc = d_sw.bind(out->sw_dir_cor_sum, out->sw_dir_cor_sum ? nc : 0))) return rc;
+    if ((rc = d_lit.bind(out->sunlit_sum, out->sunlit_sum ? nc : 0))) return rc;
+    if (d_sw.owned) scratch += nc * sizeof(float);
+    if (d_lit.owned) scratch += nc * sizeof(float);
+    HorisunArgs a;
+    a.hori = t->hori; a.vert = (const float *)t->vert;
+    a.vec_tilt = (const float *)t->tilt; a.vec_norm = (const float *)t->norm; a.vec_north = (const float *)t->north;
+    a.surf_enl_fac = (const float *)t->enl; a.mask = (const uint8_t *)t->mask;
+    a.cells = nc; a.azim_num = t->azim_num;
+    a.fill = t->fill; a.dot_prod_min = cosf(deg2rad_f(t->ang_max));            // shadow_comp.cpp:498
+    a.acc_sw = out->sw_dir_cor_sum ? static_cast<double *>(acc.p) : nullptr;
+    a.acc_lit = out->sunlit_sum ? static_cast<double *>(acc.p) + (out->sw_dir_cor_sum ? nc : 0) : nullptr;
+    a.sum_sw = d_sw.dev; a.sum_lit = d_lit.dev;
+    float ms = 0.0f;
+    {
+        hipEvent_t e0, e1;
+        HZ_HIP(hipEventCreate(&e0)); HZ_HIP(hipEventCreate(&e1));
+        struct EvFree { hipEvent_t a, b; ~EvFree() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_free{e0, e1};
+        HZ_HIP(hipEventRecord(e0, st));
+        for (int c = 0; c < plan.num_chunks; c++) {
+            int s0 = 0, kc = 0;
+            horisun_chunk(plan, num_sun, c, &s0, &kc);
+            if (sun_on_dev) a.suns = sun_positions + 3 * (size_t)s0;
+            else {
+                HZ_HIP(hipMemcpyAsync(stage_sun, sun_positions + 3 * (size_t)s0, (size_t)kc * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+                a.suns = stage_sun;
+            }
+            a.weights = nullptr;
+            if (use_w && w_on_dev) a.weights = weights + s0;
+            else if (use_w) {
+                HZ_HIP(hipMemcpyAsync(stage_w, weights + s0, (size_t)kc * sizeof(float), hipMemcpyHostToDevice, st));
+                a.weights = stage_w;
+            }
+            a.num_sun = kc;
+            a.out_u8 = d_u8.dev ? d_u8.dev + nc * (size_t)s0 : nullptr;
+            a.out_f32 = d_f32.dev ? d_f32.dev + nc * (size_t)s0 : nullptr;
+            a.first = c == 0; a.last = c == plan.num_chunks - 1;
+            if ((rc = horisun_launch(a, plan.blocks, st))) return rc;
+        }
+        HZ_HIP(hipEventRecord(e1, st));
+        HZ_HIP(hipEventSynchronize(e1));
+        HZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+    }
+    Timer t_d2h; t_d2h.start();
+    if ((rc = d_u8.finish(st))) return rc;
+    if ((rc = d_f32.finish(st))) return rc;
+    if ((rc = d_sw.finish(st))) return rc;
+    if ((rc = d_lit.finish(st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    if (stats) {
+        stats->num_cells = nc;
+        stats->t_kernel_s += (double)ms * 1e-3;
+        stats->t_d2h_s += t_d2h.stop();
+        stats->t_total_s += t_total.stop();
+        stats->scratch_bytes = scratch;
+    }
+    return HZ_OK;
+}
+
+int hz_horizon_terrain_destroy(hz_horizon_terrain *terrain) {
+    HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
+    if (!t) return HZ_OK;
+    horisun_release(t);
+    stream_release(t->device, t->stream);
     delete t;
     return HZ_OK;
 }

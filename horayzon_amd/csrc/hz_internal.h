@@ -30,6 +30,7 @@ extern std::atomic<int> g_shadow_fast_cap;   // entries of k_shadow_refill's fas
 extern std::atomic<int> g_topo_wide;         // 1: the reductions over the azimuth axis use the fallback kernel k_topo_wide
 extern std::atomic<int> g_accum_chunk;       // > 0: sun positions per chunk of hz_terrain_accumulate (default 0: from the memory budget)
 extern std::atomic<int> g_coarse_tile;       // > 0: cells of k_coarse_reduce's LDS tile, at most the default (hz_subgrid.hip; default 0)
+extern std::atomic<int> g_horisun_chunk;     // > 0: sun positions per launch of hz_horizon_terrain_run (default 0: HZ_HORISUN_CHUNK)
 
 #define HZ_HIP(expr)                                                                      \
     do {                                                                                  \
@@ -244,6 +245,27 @@ int accum_final_launch(const uint8_t *mask, size_t n, float fill, const double *
 int coarse_count_launch(const uint8_t *mask, int dim_0, int dim_1, int p0, int p1, unsigned *n, hipStream_t st);
 int coarse_reduce_launch(const uint8_t *codes, const float *vals, const uint8_t *mask, const unsigned *n, int dim_0, int dim_1,
                          int p0, int p1, int k, float fill, float *f_cor, float *lit, hipStream_t st);
+
+// hz_horisun.hip (hz_horizon_terrain_run; device pointers): one launch of k_horisun over num_sun positions, one lane per cell.
+// Per-position maps out_u8 / out_f32 [num_sun][cells] (null: not wanted).  Sums (sum_sw / sum_lit f32[cells], null: not
+// wanted): the lane's float64 sums start at 0 (first) or at acc_sw / acc_lit f64[cells], take w[s] * value in ascending s and
+// go back to acc_* or, in the last launch of a call, rounded once to sum_* (masked cells: fill)
+struct HorisunArgs {
+    const float *hori;                   // f32[cells][azim_num]
+    const float *vert;                   // f32[cells][3]: the vertices of the inner domain
+    const float *vec_tilt, *vec_norm, *vec_north, *surf_enl_fac;
+    const uint8_t *mask;
+    size_t cells;
+    int azim_num;
+    const float *suns, *weights;         // f32[num_sun][3], f32[num_sun] or null = ones
+    int num_sun;
+    float fill, dot_prod_min;
+    uint8_t *out_u8; float *out_f32;
+    double *acc_sw, *acc_lit;
+    float *sum_sw, *sum_lit;
+    int first, last;
+};
+int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st);
 
 // hz_sort.hip: hand-written stable LSD radix sort (pairs) and exclusive scan, uint32
 size_t sort_temp_elems(size_t n);

@@ -294,3 +294,207 @@ class Terrain:
         _lib.check(_lib.lib().hz_terrain_sw_dir_cor_coarse(
             self._h, ptr(sun_positions), sun_positions.shape[0], p0, p1, ptr(f_cor), ptr(sunlit_frac), C.byref(st)))
         self.last_stats = st.as_dict()
+
+
+def _is_tensor(a):
+    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+
+
+def gridded_azimuths(azim_num):
+    """The azimuth array ``horizon_gridded`` returns for ``azim_num`` directions: float32 of 2 pi k / azim_num."""
+    azim = np.empty(azim_num, dtype=np.float32)
+    for i in range(azim_num):
+        azim[i] = ((2 * np.pi) / azim_num * i)
+    return azim
+
+
+class HorizonTerrain:
+    """``Terrain``'s answers from a stored horizon instead of a ray (additive, not in the reference): a cell is
+    terrain-shaded when the sun's elevation in the cell's frame is below the horizon ``hori`` of ``horizon_gridded``,
+    interpolated linearly at the sun's azimuth (clause 10).  No scene and no BVH; the self-shading and
+    ``ang_max`` tests, the shadow codes, the ``sw_dir_cor`` formula and the sums of ``accumulate`` are ``Terrain``'s, and so
+    are the method names and signatures.  Atmospheric refraction is not covered: there is no ``refrac_cor`` and no
+    ``elevation`` argument."""
+
+    def __init__(self, *, device=0):
+        self._h = C.c_void_p()
+        self._shape = None
+        self._hori = None
+        self.device = device
+        self.last_stats = None
+        _lib.check(_lib.lib().hz_horizon_terrain_create(device, C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib.lib().hz_horizon_terrain_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _typed_hori(self, hori):
+        """``hori``: a NumPy array, or a torch tensor on the object's GPU (borrowed: the object holds a reference)."""
+        if isinstance(hori, np.ndarray):
+            _typed(hori, np.float32, 3, "hori")
+            return
+        if not hasattr(hori, "data_ptr"):
+            raise TypeError("Argument 'hori' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
+                            % type(hori).__name__)
+        if hori.dim() != 3:
+            raise ValueError("Buffer has wrong number of dimensions (expected 3, got %d)" % hori.dim())
+        if str(hori.dtype).split(".")[-1] != "float32":
+            raise ValueError("Buffer dtype mismatch, expected 'float32' but got '%s'" % hori.dtype)
+        if hori.device.type != "cuda" or hori.device.index != self.device:
+            raise ValueError("tensor 'hori' is not on the HorizonTerrain's device (cuda:%d)" % self.device)
+
+    def initialise(self, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                   vec_tilt, vec_norm, vec_north, surf_enl_fac, mask,
+                   sw_dir_cor_fill=np.nan, ang_max=89.0):
+        """Initialise with the horizon ``hori`` f32 (y, x, azim_num) [radian] and ``azim`` as ``horizon_gridded`` returns
+        them (``azim[k] = 2 pi k / azim_num`` is the only layout supported; azim_num >= 1), the DEM vertices and the
+        per-cell arrays of ``Terrain.initialise`` plus ``vec_north``.  ``hori`` is a NumPy array (copied to the GPU) or a
+        torch tensor on the object's GPU (borrowed: the object holds a reference, the data must not change while it is in
+        use); the other arrays are NumPy and are copied.  No atmospheric refraction (no ``refrac_cor`` / ``elevation``)."""
+        _typed(azim, np.float32, 1, "azim")
+        self._typed_hori(hori)
+        _typed(vert_grid, np.float32, 1, "vert_grid")
+        _typed(vec_tilt, np.float32, 3, "vec_tilt")
+        _typed(vec_norm, np.float32, 3, "vec_norm")
+        _typed(vec_north, np.float32, 3, "vec_north")
+        _typed(surf_enl_fac, np.float32, 2, "surf_enl_fac")
+        _typed(mask, np.uint8, 2, "mask")
+
+        vectors = (vec_tilt, vec_norm, vec_north)
+        host = [a for a in (azim, hori, vert_grid, vec_tilt, vec_norm, vec_north, surf_enl_fac, mask) if not _is_tensor(a)]
+        V.run((
+            (ValueError, "inconsistency between input arguments 'vert_grid', 'dem_dim_0' and 'dem_dim_1'",
+             lambda: not V.fits_grid(len(vert_grid), dem_dim_0, dem_dim_1)),
+            (ValueError, "inconsistency between input arguments 'dem_dim_0', 'dem_dim_1', 'offset_0', 'offset_1' and 'vec_norm'",
+             lambda: not V.window_inside(offset_0, offset_1, vec_tilt.shape, dem_dim_0, dem_dim_1)),
+            (ValueError, "Inconsistent/incorrect shape of 'vec_tilt', 'vec_norm' and/or 'vec_north'",
+             lambda: not V.same_leading_shape(vectors, 3, 3) or vec_tilt.shape[2] != 3),
+            (ValueError, "Inconsistent/incorrect shape of 'surf_enl_fac' and/or 'mask'",
+             lambda: not V.same_leading_shape((vec_tilt[..., 0], surf_enl_fac, mask), 2, 2)),
+            (ValueError, "Inconsistent/incorrect shape of 'hori'",
+             lambda: tuple(hori.shape[:2]) != vec_tilt.shape[:2] or hori.shape[2] < 1),
+            (ValueError, "'azim' is not the azimuth array of horizon_gridded",
+             lambda: azim.shape[0] != hori.shape[2] or not np.array_equal(azim, gridded_azimuths(hori.shape[2]))),
+            (ValueError, "not all input arrays are C-contiguous",
+             lambda: not all(a.flags["C_CONTIGUOUS"] for a in host) or (_is_tensor(hori) and not hori.is_contiguous())),
+            (ValueError, "Vectors in 'vec_tilt', 'vec_norm' and/or 'vec_north' are not normalised",
+             lambda: not all(V.unit_vectors(v) for v in vectors)),
+            (TypeError, "'ang_max' must be in the range [85.0, 89.99]", lambda: ang_max < 85.0 or ang_max > 89.99),
+            (ValueError, V.MSG_DIM_LIMIT, lambda: max(dem_dim_0, dem_dim_1) > V.DIM_LIMIT),
+        ))
+
+        st = hz_stats()
+        self._shape = None
+        _lib.check(_lib.lib().hz_horizon_terrain_initialise(
+            self._h, ptr(hori), hori.shape[2], ptr(vert_grid), dem_dim_0, dem_dim_1, offset_0, offset_1,
+            ptr(vec_tilt), ptr(vec_norm), ptr(vec_north), vec_tilt.shape[0], vec_tilt.shape[1],
+            ptr(surf_enl_fac), ptr(mask), sw_dir_cor_fill, ang_max, C.byref(st)))
+        self._hori = hori if _is_tensor(hori) else None      # keep a borrowed horizon alive
+        self._shape = (vec_tilt.shape[0], vec_tilt.shape[1])
+        self.last_stats = st.as_dict()
+
+    _batch_out = staticmethod(Terrain._batch_out)
+    _accum_arg = Terrain._accum_arg
+
+    def _check_out(self, buf, name):
+        if self._shape is None:
+            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
+        if tuple(buf.shape[-2:]) != self._shape:
+            raise ValueError("array '%s' has incorrect shape" % name)
+
+    def _run(self, sun_positions, weights, num_sun, **outs):
+        st = hz_stats()
+        out = _lib.hz_horisun_out(**{k: ptr(v) for k, v in outs.items()})
+        _lib.check(_lib.lib().hz_horizon_terrain_run(self._h, ptr(sun_positions), ptr(weights), num_sun,
+                                                     C.byref(out), C.byref(st)))
+        self.last_stats = st.as_dict()
+
+    def shadow(self, sun_position, shadow_buffer):
+        """Compute shadow mask for specified sun position
+        (0: illuminated, 1: self-shaded, 2: terrain-shaded, 3: masked)."""
+        _typed(sun_position, np.float32, 1, "sun_position")
+        _typed(shadow_buffer, np.uint8, 2, "shadow_buffer")
+        if (sun_position.ndim != 1) or (sun_position.size != 3):
+            raise ValueError("array 'sun_position' has incorrect shape")
+        if not shadow_buffer.flags["C_CONTIGUOUS"]:
+            raise ValueError("array 'shadow_buffer' is not C-contiguous")
+        self._check_out(shadow_buffer, "shadow_buffer")
+        self._run(np.ascontiguousarray(sun_position), None, 1, shadow=shadow_buffer)
+
+    def sw_dir_cor(self, sun_position, sw_dir_cor_buffer):
+        """Compute shortwave correction factor for specified sun position."""
+        _typed(sun_position, np.float32, 1, "sun_position")
+        _typed(sw_dir_cor_buffer, np.float32, 2, "sw_dir_cor_buffer")
+        if (sun_position.ndim != 1) or (sun_position.size != 3):
+            raise ValueError("array 'sun_position' has incorrect shape")
+        if not sw_dir_cor_buffer.flags["C_CONTIGUOUS"]:
+            raise ValueError("array 'sw_dir_cor_buffer' is not C-contiguous")
+        self._check_out(sw_dir_cor_buffer, "sw_dir_cor_buffer")
+        self._run(np.ascontiguousarray(sun_position), None, 1, sw_dir_cor=sw_dir_cor_buffer)
+
+    def shadow_batch(self, sun_positions, shadow_buffers):
+        """``shadow`` for sun_positions f32[num][3] -> shadow_buffers u8[num][y][x] (NumPy or torch/HBM)."""
+        _typed(sun_positions, np.float32, 2, "sun_positions")
+        self._batch_out(shadow_buffers, np.uint8, "shadow_buffers")
+        if sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1 or shadow_buffers.shape[0] != sun_positions.shape[0]:
+            raise ValueError("array 'sun_positions' has incorrect shape")
+        self._check_out(shadow_buffers, "shadow_buffers")
+        self._run(np.ascontiguousarray(sun_positions), None, sun_positions.shape[0], shadow=shadow_buffers)
+
+    def sw_dir_cor_batch(self, sun_positions, sw_dir_cor_buffers):
+        """``sw_dir_cor`` for sun_positions f32[num][3] -> sw_dir_cor_buffers f32[num][y][x] (NumPy or torch/HBM)."""
+        _typed(sun_positions, np.float32, 2, "sun_positions")
+        self._batch_out(sw_dir_cor_buffers, np.float32, "sw_dir_cor_buffers")
+        if sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1 or sw_dir_cor_buffers.shape[0] != sun_positions.shape[0]:
+            raise ValueError("array 'sun_positions' has incorrect shape")
+        self._check_out(sw_dir_cor_buffers, "sw_dir_cor_buffers")
+        self._run(np.ascontiguousarray(sun_positions), None, sun_positions.shape[0], sw_dir_cor=sw_dir_cor_buffers)
+
+    def accumulate(self, sun_positions, weights=None, *, sw_dir_cor_sum=None, sunlit_sum=None,
+                   shadow_buffers=None, sw_dir_cor_buffers=None):
+        """``Terrain.accumulate`` from the horizon: ``sw_dir_cor_sum`` = sum of weights[s] * sw_dir_cor(sun_positions[s]) and
+        ``sunlit_sum`` = sum of weights[s] over the positions for which shadow() gives 0, per cell, accumulated in float64
+        in ascending s and rounded to float32 once; masked cells get ``sw_dir_cor_fill``.  sun_positions f32[S][3] (S >= 1),
+        weights f32[S] (None: ones); outputs f32[y][x], NumPy or torch tensors on the object's GPU; at least one.  The sums
+        stay in registers: device memory besides the buffers does not grow with S (``last_stats["scratch_bytes"]``).
+        ``shadow_buffers`` u8[S][y][x] and ``sw_dir_cor_buffers`` f32[S][y][x] (keyword only, not in ``Terrain``; NumPy or
+        torch/HBM) also take the per-position maps of the same pass."""
+        outs = (("sw_dir_cor_sum", sw_dir_cor_sum), ("sunlit_sum", sunlit_sum))
+        self._accum_arg(sun_positions, 2, "sun_positions")
+        if weights is not None:
+            self._accum_arg(weights, 1, "weights")
+        for name, buf in outs:
+            if buf is not None:
+                self._accum_arg(buf, 2, name)
+        if shadow_buffers is not None:
+            self._batch_out(shadow_buffers, np.uint8, "shadow_buffers")
+        if sw_dir_cor_buffers is not None:
+            self._batch_out(sw_dir_cor_buffers, np.float32, "sw_dir_cor_buffers")
+        maps = [(n, b) for n, b in (("shadow_buffers", shadow_buffers), ("sw_dir_cor_buffers", sw_dir_cor_buffers))
+                if b is not None]
+        given = [buf for _, buf in outs if buf is not None]
+        arrays = [sun_positions] + ([weights] if weights is not None else []) + given
+
+        def contiguous(a):
+            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
+        V.run((
+            (ValueError, "at least one of 'sw_dir_cor_sum' and 'sunlit_sum' must be given", lambda: not given),
+            (ValueError, "array 'sun_positions' has incorrect shape",
+             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
+            (ValueError, "array 'weights' has incorrect shape",
+             lambda: weights is not None and weights.shape[0] != sun_positions.shape[0]),
+            (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in arrays)),
+            (ValueError, "'sw_dir_cor_sum' and 'sunlit_sum' must be different arrays",
+             lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
+            (ValueError, "array 'shadow_buffers' / 'sw_dir_cor_buffers' has incorrect shape",
+             lambda: any(b.shape[0] != sun_positions.shape[0] for _, b in maps)),
+        ))
+        for name, buf in tuple(outs) + tuple(maps):
+            if buf is not None:
+                self._check_out(buf, name)
+        self._run(sun_positions, weights, sun_positions.shape[0], sw_dir_cor_sum=sw_dir_cor_sum, sunlit_sum=sunlit_sum,
+                  shadow=shadow_buffers, sw_dir_cor=sw_dir_cor_buffers)

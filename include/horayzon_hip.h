@@ -304,7 +304,7 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* over the azimuth axis use the one-lane-per-cell fallback kernel, "accum_chunk" = sun positions per chunk of                   */
 /* hz_terrain_accumulate and hz_terrain_sw_dir_cor_coarse (<= 0: the default, from the scratch budget), "coarse_tile" = cells   */
 /* of the LDS tile of hz_terrain_sw_dir_cor_coarse's reduction (<= 0 or above the default: the default; blocks wider than the  */
-/* tile take the kernel without LDS)                                                                                            */
+/* tile take the kernel without LDS), "horisun_chunk" = sun positions per launch of hz_horizon_terrain_run (<= 0: the default)  */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */
@@ -419,6 +419,43 @@ int hz_terrain_sw_dir_cor_coarse(hz_terrain *terrain, const float *sun_positions
 int hz_terrain_count_work(hz_terrain *terrain, int on);
 /* CppTerrain::~CppTerrain, shadow_comp.cpp:310-316 */
 int hz_terrain_destroy(hz_terrain *terrain);
+
+/* ------------------------------------------------------------------------- */
+/* Shadow from a stored horizon (additive; no BVH, no ray): the handle API of hz_terrain with the look-up       */
+/* "the sun's elevation against the horizon at the sun's azimuth" in place of the ray.  Per unmasked cell and    */
+/* position p (no atmospheric refraction):                                                                      */
+/*   float32, as hz_terrain: o = v + norm * 0.05f, s = unit(p - o), dot_ns = (n.s), dot_ts = (tilt.s), sums      */
+/*     associated (x + y) + z; shadow = 1 where !(dot_ts > 0), sw_dir_cor = 0 where !(dot_ts > dot_prod_min);     */
+/*   float64 from the float32 s, norm, north, every product and sum rounded on its own: E = north x norm,        */
+/*     cn = s.north, ce = s.E, cu = s.norm (x, y, z order), phi = atan2(ce, cn) (+ 2 pi if < 0),                 */
+/*     u = phi * (A / (2 pi)), k = floor(u), t = u - k, h = (1 - t) * hori[k mod A] + t * hori[(k + 1) mod A],   */
+/*     alpha = asin(min(max(cu, -1), 1)); terrain-shaded iff alpha < h (a NaN h: lit).                           */
+/*   shadow 0 / 1 / 2 / 3 and sw_dir_cor = (dot_ts / max(dot_ns, dot_prod_min)) * surf_enl_fac or 0 as           */
+/*   hz_terrain_shadow / _sw_dir_cor with "terrain-shaded" for "the ray hit"; the sums as hz_terrain_accumulate. */
+/* hori f32[dim_in_0][dim_in_1][azim_num] [rad] for the azimuths 2 pi k / azim_num (what hz_horizon_gridded      */
+/* writes); azim_num >= 1.  A device pointer `hori` is BORROWED (the caller keeps it alive until the handle is   */
+/* initialised again or destroyed); a host `hori` and every other input, host or device, is copied.             */
+/* ------------------------------------------------------------------------- */
+typedef struct hz_horizon_terrain hz_horizon_terrain;
+typedef struct hz_horisun_out {
+    int32_t size;            /* sizeof(hz_horisun_out) */
+    uint8_t* shadow;         /* u8 [num_sun][y][x], optional */
+    float*   sw_dir_cor;     /* f32[num_sun][y][x], optional */
+    float*   sw_dir_cor_sum; /* f32[y][x], optional (weighted) */
+    float*   sunlit_sum;     /* f32[y][x], optional (weighted) */
+} hz_horisun_out;
+int hz_horizon_terrain_create(int device, hz_horizon_terrain** t);
+int hz_horizon_terrain_initialise(hz_horizon_terrain* t, const float* hori, int azim_num,
+        const float* vert_grid, int dem_dim_0, int dem_dim_1, int offset_0, int offset_1,
+        const float* vec_tilt, const float* vec_norm, const float* vec_north, int dim_in_0, int dim_in_1,
+        const float* surf_enl_fac, const uint8_t* mask, float sw_dir_cor_fill, float ang_max, hz_stats* stats);
+/* Any subset of the four outputs (at least one; NULL = not wanted; host or device pointers, all different) from  */
+/* one pass: positions go in chunks, one launch per chunk.  weights f32[num_sun], NULL = ones (the sums only).   */
+/* stats (may be NULL): t_kernel_s, t_d2h_s, t_total_s, num_cells, scratch_bytes = device memory of the call      */
+/* besides per-position maps staged for host outputs; it does not grow with num_sun                             */
+int hz_horizon_terrain_run(hz_horizon_terrain* t, const float* sun_positions, const float* weights /* NULL = ones */,
+        int num_sun, const hz_horisun_out* out, hz_stats* stats);
+int hz_horizon_terrain_destroy(hz_horizon_terrain* t);
 
 /* ------------------------------------------------------------------------- */
 /* Ocean masking: the `mask` argument of the entry points above, from a land-sea mask and the coastline        */

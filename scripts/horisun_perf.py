@@ -1,0 +1,181 @@
+"""HorizonTerrain on the c3 tile (3601^2, 360 azimuths, the 144 sun positions of synth.sun_positions), everything resident in
+HBM, against Terrain's ray casting of the same commit on the same box in the same run.
+
+    python scripts/horisun_perf.py [--tile N] [--suns S] [--window W] [--out FILE]
+    python scripts/horisun_perf.py --pmc            # only HorizonTerrain.sw_dir_cor_batch, for a counter run of its own:
+        rocprofv3 --pmc FETCH_SIZE --output-format csv -d <dir> -- python scripts/horisun_perf.py --pmc
+
+The tile's own horizon (guess_constant, dist_search 50 km, hori_acc 0.25 deg) is computed into a torch tensor in HBM and
+borrowed by HorizonTerrain.  One warm-up and one timed pass of each call; one JSON line per figure:
+  (a) sw_dir_cor_batch / shadow_batch / accumulate of HorizonTerrain and of Terrain, kernel ms per position (HIP events,
+      last_stats) and wall ms; the float64 NumPy look-up on the host for a W x W window, ms per position, scaled by cells;
+  (b) the bytes of horizon the batch must touch: the distinct 128-byte lines over all positions, counted from the float64
+      look-up on the window and scaled to the tile (the achieved bytes come from the --pmc run: FETCH_SIZE of k_horisun,
+      doubled as for every wide read on gfx950);
+  (c) the share of unmasked (cell, position) pairs on which HorizonTerrain.shadow and Terrain.shadow agree -- a reported
+      figure: the interpolated horizon is another model than a ray.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def timed(fn):
+    """One warm-up, one timed pass: (result of the timed pass, its wall seconds)."""
+    fn()
+    t0 = time.perf_counter()
+    r = fn()
+    return r, time.perf_counter() - t0
+
+
+def host_lookup(suns, hori, vert, vec_tilt, vec_norm, vec_north):
+    """The look-up of DESIGN.md section 4 clause 10 in float64 NumPy on a window (set-up in float64 too: a speed and traffic
+    yardstick, not the bit-exact reference of tests/horisun_reference.py).  Returns (shadow codes u8[S][y][x], the set of
+    distinct (cell, 128-byte line of its row) pairs touched, as a count)."""
+    A = hori.shape[2]
+    n0, n1 = hori.shape[:2]
+    o = vert.astype(np.float64) + 0.05 * vec_norm
+    east = np.cross(vec_north.astype(np.float64), vec_norm.astype(np.float64))
+    codes = np.empty((suns.shape[0], n0, n1), np.uint8)
+    lines_per_row = (A * 4 + 127) // 128 + 1
+    touched = np.zeros((n0, n1, lines_per_row), bool)
+    row_byte0 = (np.arange(n0 * n1, dtype=np.int64).reshape(n0, n1) * A * 4) % 128      # offset of the row in its first line
+    ii, jj = np.meshgrid(np.arange(n0), np.arange(n1), indexing="ij")
+    for s in range(suns.shape[0]):
+        d = suns[s].astype(np.float64) - o
+        d /= np.linalg.norm(d, axis=2, keepdims=True)
+        dot_ts = (vec_tilt * d).sum(axis=2)
+        cn, ce, cu = (d * vec_north).sum(axis=2), (d * east).sum(axis=2), (d * vec_norm).sum(axis=2)
+        phi = np.arctan2(ce, cn)
+        phi[phi < 0.0] += 2.0 * np.pi
+        u = phi * (A / (2.0 * np.pi))
+        k = np.clip(np.floor(u), 0, A).astype(np.int64)
+        t = u - k
+        k0, k1 = k % A, (k + 1) % A
+        h = (1.0 - t) * np.take_along_axis(hori, k0[..., None], 2)[..., 0] + t * np.take_along_axis(hori, k1[..., None], 2)[..., 0]
+        shaded = np.arcsin(np.clip(cu, -1.0, 1.0)) < h
+        faces = dot_ts > 0.0
+        codes[s] = np.where(faces, np.where(shaded, 2, 0), 1)
+        for kk in (k0, k1):
+            line = (row_byte0 + kk * 4) // 128
+            touched[ii[faces], jj[faces], line[faces]] = True
+    return codes, int(touched.sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tile", type=int, default=3601)
+    ap.add_argument("--suns", type=int, default=144)
+    ap.add_argument("--azim", type=int, default=360)
+    ap.add_argument("--window", type=int, default=512)
+    ap.add_argument("--dist-search", type=float, default=50.0)
+    ap.add_argument("--pmc", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import horayzon_amd as hz
+    from horayzon_amd import _lib, synth
+    from horayzon_amd.shadow import gridded_azimuths
+    n, off, A = args.tile, 16, args.azim
+    g = synth.fractal_tile(n=n, offset=off)
+    in0 = in1 = n - 2 * off
+    vec_tilt, enl = synth.tilt_from_planar_dem(g["x"], g["y"], g["z"], off)
+    vec_norm, vec_north = synth.planar_frames(in0, in1)
+    elev = np.ascontiguousarray(g["z"][off:off + in0, off:off + in1], np.float32)
+    mask = np.ones((in0, in1), np.uint8)
+    suns, _, _ = synth.sun_positions(num=args.suns)
+    S = suns.shape[0]
+    shape = mask.shape
+    dev = "cuda:0"
+    lines = []
+
+    def emit(d):
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+
+    # the tile's own horizon, written straight into HBM
+    L = _lib.lib()
+    scene = hz.Scene.create(g["vert_grid"], n, n)
+    d_hori = torch.empty((in0, in1, A), dtype=torch.float32, device=dev)
+    d_mask = torch.from_numpy(mask).to(dev)
+    torch.cuda.synchronize()
+    opts = _lib.hz_opts()
+    opts.device, opts.top_nodes, opts.regroup = 0, -1, -1
+    st = _lib.hz_stats()
+    _lib.check(L.hz_horizon_gridded_scene(scene._h, _lib.ptr(vec_norm), _lib.ptr(vec_north), off, off, d_hori.data_ptr(),
+                                          in0, in1, A, args.dist_search, 0.25, b"guess_constant", -15.0, d_mask.data_ptr(),
+                                          0.0, 0.01, C.byref(opts), C.byref(st)))
+    emit({"figure": "horizon", "tile": n, "azim_num": A, "t_kernel_ms": round(1e3 * st.t_kernel_s, 1),
+          "hori_bytes": int(d_hori.numel()) * 4})
+
+    th = hz.shadow.HorizonTerrain()
+    th.initialise(gridded_azimuths(A), d_hori, g["vert_grid"], n, n, off, off, vec_tilt, vec_norm, vec_north, enl, mask,
+                  sw_dir_cor_fill=-7.0)
+    d_sw = torch.empty((S,) + shape, dtype=torch.float32, device=dev)
+    if args.pmc:
+        timed(lambda: th.sw_dir_cor_batch(suns, d_sw))
+        return
+    tr = hz.shadow.Terrain()
+    tr.initialise(g["vert_grid"], n, n, off, off, vec_tilt, vec_norm, enl, elev, mask, sw_dir_cor_fill=-7.0, scene=scene)
+    d_sh = {"HorizonTerrain": torch.empty((S,) + shape, dtype=torch.uint8, device=dev),
+            "Terrain": torch.empty((S,) + shape, dtype=torch.uint8, device=dev)}
+    d_sum = torch.empty(shape, dtype=torch.float32, device=dev)
+    d_lit = torch.empty(shape, dtype=torch.float32, device=dev)
+    d_suns = torch.from_numpy(suns).to(dev)
+    torch.cuda.synchronize()
+
+    # (a) speed: the two classes alternate call by call
+    for call in ("sw_dir_cor_batch", "shadow_batch", "accumulate"):
+        for name, t in (("HorizonTerrain", th), ("Terrain", tr)):
+            if call == "sw_dir_cor_batch":
+                fn = lambda: t.sw_dir_cor_batch(suns, d_sw)
+            elif call == "shadow_batch":
+                fn = lambda: t.shadow_batch(suns, d_sh[name])
+            else:
+                fn = lambda: t.accumulate(d_suns, None, sw_dir_cor_sum=d_sum, sunlit_sum=d_lit)
+            _, wall = timed(fn)
+            torch.cuda.synchronize()
+            emit({"figure": "speed", "class": name, "call": call, "tile": n, "suns": S,
+                  "kernel_ms_per_position": round(1e3 * t.last_stats["t_kernel_s"] / S, 4),
+                  "wall_ms_per_position": round(1e3 * wall / S, 4), "scratch_bytes": t.last_stats["scratch_bytes"]})
+
+    # (c) agreement of the look-up with ray casting on the tile's own horizon
+    same = 0
+    for s in range(S):
+        same += int((d_sh["HorizonTerrain"][s] == d_sh["Terrain"][s]).sum())
+    emit({"figure": "agreement_with_ray_casting", "pairs": S * in0 * in1, "share_equal": round(same / (S * in0 * in1), 6)})
+
+    # host look-up on a window (second comparison of (a)) and the lines it touches (b)
+    W = min(args.window, in0)
+    r0 = c0 = (in0 - W) // 2
+    win = (slice(r0, r0 + W), slice(c0, c0 + W))
+    hori_w = d_hori[r0:r0 + W, c0:c0 + W].cpu().numpy().astype(np.float64)
+    verts = g["vert_grid"][:3 * n * n].reshape(n, n, 3)[off:off + in0, off:off + in1]
+    t0 = time.perf_counter()
+    codes_w, touched = host_lookup(suns, hori_w, verts[win], vec_tilt[win].astype(np.float64),
+                                   vec_norm[win].astype(np.float64), vec_north[win].astype(np.float64))
+    wall = time.perf_counter() - t0
+    scale = (in0 * in1) / float(W * W)
+    emit({"figure": "host_numpy_lookup", "window": W, "ms_per_position_window": round(1e3 * wall / S, 2),
+          "ms_per_position_scaled_to_tile": round(1e3 * wall / S * scale, 1),
+          "share_equal_to_gpu_codes": round(float((codes_w == d_sh["HorizonTerrain"][:, r0:r0 + W, c0:c0 + W].cpu().numpy()).mean()), 6)})
+    emit({"figure": "horizon_lines", "window": W, "distinct_128B_lines_window": touched,
+          "bytes_scaled_to_tile": int(touched * 128 * scale), "hori_bytes": int(d_hori.numel()) * 4,
+          "output_bytes_sw_dir_cor_batch": S * in0 * in1 * 4})
+    if args.out:
+        with open(args.out, "w") as f:
+            for d in lines:
+                f.write(json.dumps(d) + "\n")
+
+
+if __name__ == "__main__":
+    main()
