@@ -87,6 +87,8 @@ SYMBOLS = (
     "hz_terrain_accumulate", "hz_terrain_sw_dir_cor_coarse",
     "hz_coastline_distance", "hz_coastline_buffer",
     "hz_horizon_terrain_create", "hz_horizon_terrain_initialise", "hz_horizon_terrain_run", "hz_horizon_terrain_destroy",
+    "hz_horizon_gridded_planes", "hz_horizon_gridded_scene_planes", "hz_hori_to_planes", "hz_hori_from_planes",
+    "hz_topo_params_planes", "hz_horizon_terrain_initialise_planes",
 )
 
 
@@ -144,6 +146,11 @@ def lib():
     L.hz_horizon_gridded_ex.argtypes = L.hz_horizon_gridded.argtypes[:-1] + [C.POINTER(hz_topo_out), C.POINTER(hz_stats)]
     L.hz_horizon_gridded_scene_ex.argtypes = L.hz_horizon_gridded_scene.argtypes[:-1] + [C.POINTER(hz_topo_out),
                                                                                          C.POINTER(hz_stats)]
+    L.hz_horizon_gridded_planes.argtypes = L.hz_horizon_gridded_ex.argtypes
+    L.hz_horizon_gridded_scene_planes.argtypes = L.hz_horizon_gridded_scene_ex.argtypes
+    L.hz_hori_to_planes.argtypes = [vp, ip, ip, ip, vp, ip]
+    L.hz_hori_from_planes.argtypes = [vp, ip, ip, ip, vp, ip]
+    L.hz_topo_params_planes.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp, vp, ip]
     L.hz_horizon_locations.argtypes = [
         vp, ip, ip, vp, vp, vp, vp, vp, ip, ip, C.c_float, C.c_float, C.c_char_p, C.c_char_p,
         C.c_float, vp, ip, C.POINTER(hz_opts), C.POINTER(hz_stats)]
@@ -191,6 +198,7 @@ def lib():
     L.hz_horizon_terrain_create.argtypes = [ip, C.POINTER(vp)]
     L.hz_horizon_terrain_initialise.argtypes = [vp, vp, ip, vp, ip, ip, ip, ip, vp, vp, vp, ip, ip, vp, vp,
                                                 C.c_float, C.c_float, C.POINTER(hz_stats)]
+    L.hz_horizon_terrain_initialise_planes.argtypes = L.hz_horizon_terrain_initialise.argtypes
     L.hz_horizon_terrain_run.argtypes = [vp, vp, vp, ip, C.POINTER(hz_horisun_out), C.POINTER(hz_stats)]
     L.hz_horizon_terrain_destroy.argtypes = [vp]
     for name in SYMBOLS:

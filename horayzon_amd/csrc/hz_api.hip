@@ -548,7 +548,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
                        int offset_1, float *hori_buffer, int dim_in_0, int dim_in_1, int azim_num,
                        float dist_search, float hori_acc, const char *ray_algorithm,
                        float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
-                       const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+                       const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats, float *hori_planes = nullptr) {
     int alg = 2;
     int rc = parse_alg(ray_algorithm, &alg);
     if (rc) return rc;
@@ -558,7 +558,12 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
         return set_error(HZ_ERR_ARG, "inconsistency between input arguments dem_dim_0, dem_dim_1, offset_0, offset_1 and vec_norm");
     if (!(hori_acc > 0.0f) || hori_acc > 10.0f) return set_error(HZ_ERR_ARG, "limit of hori_acc (10 degree) is exceeded");
     const bool skip_hori = opts && opts->skip_hori;
-    if (!hori_buffer && !skip_hori) return set_error(HZ_ERR_ARG, "hori_buffer is NULL");
+    // hori_planes (hz_horizon_gridded_planes): the horizon leaves as planes[azim][y][x]; the cell-major horizon lives in the
+    // chunk buffer of skip_hori only, and every chunk is transposed into its rows of every plane (hz_planes.hip)
+    const bool to_planes = hori_planes != nullptr;
+    if (to_planes && skip_hori) return set_error(HZ_ERR_ARG, "skip_hori with hori_planes: there is nothing to lay out");
+    if (to_planes) hori_buffer = nullptr;
+    if (!hori_buffer && !skip_hori && !to_planes) return set_error(HZ_ERR_ARG, "hori_buffer is NULL");
     if (opts && opts->svf && !opts->vec_tilt) return set_error(HZ_ERR_ARG, "opts.svf needs opts.vec_tilt");
     // the SVF weights sectors by azim[1] - azim[0] (topo_param.pyx:433): undefined for a single azimuth
     if (opts && opts->svf && azim_num < 2) return set_error(HZ_ERR_ARG, "opts.svf needs azim_num >= 2");
@@ -643,13 +648,20 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     size_t tmp_bytes = 0;         // chunk buffers of a host / skipped hori_buffer (hz_stats.scratch_bytes)
     struct TmpFree { void **p; ~TmpFree() { if (*p) (void)hipFree(*p); } } tmp_free{&tmp_hori}, tmp_free2{&tmp_hori2};
     const size_t row_bytes = (size_t)dim_in_1 * azim_num * 4;
-    const bool stream_out = !skip_hori && !is_device_ptr(hori_slab_host);
-    if (skip_hori || stream_out) {
+    const bool stream_out = !skip_hori && !to_planes && !is_device_ptr(hori_slab_host);
+    // planes: stride of one plane and the plane element of the slab's first cell, by the rules of hori_buffer
+    const size_t plane_stride = hori_is_slab ? slab_cells : ncell;
+    const size_t plane_cell0 = hori_is_slab ? 0 : (size_t)row_begin * dim_in_1;
+    const bool planes_on_dev = to_planes && is_device_ptr(hori_planes);
+    void *tmp_planes = nullptr;   // chunk of planes [azim_num][chunk cells] on its way to a host hori_planes
+    TmpFree tmp_free3{&tmp_planes};
+    if (skip_hori || to_planes || stream_out) {
         if (skip_hori && !want_topo) return set_error(HZ_ERR_ARG, "skip_hori without svf, vsf or openness: nothing to compute");
         if ((rc = alloc_hori_chunk(row_end - row_begin, row_bytes, skip_hori, (opts && opts->chunk_rows > 0) ? opts->chunk_rows : 0, &chunk_rows, &tmp_hori)))
             return rc;
         tmp_bytes = (size_t)chunk_rows * row_bytes;
         if (stream_out && chunk_rows < row_end - row_begin) { HZ_HIP(hipMalloc(&tmp_hori2, (size_t)chunk_rows * row_bytes)); tmp_bytes *= 2; }
+        if (to_planes && !planes_on_dev) { HZ_HIP(hipMalloc(&tmp_planes, (size_t)chunk_rows * row_bytes)); tmp_bytes *= 2; }
     } else {
         if ((rc = d_hori.bind(hori_slab_host, slab_cells * (size_t)azim_num))) return rc;
     }
@@ -786,7 +798,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
         // the kernels index hori by global cell: shift the (slab- or chunk-local) buffer back
         float *hori_chunk;
         if (stream_out) hori_chunk = (float *)((n_chunk & 1) ? tmp_hori2 : tmp_hori);
-        else if (skip_hori) hori_chunk = (float *)tmp_hori;
+        else if (skip_hori || to_planes) hori_chunk = (float *)tmp_hori;
         else hori_chunk = d_hori.dev + (size_t)(rb - row_begin) * dim_in_1 * azim_num;
         a.hori = hori_chunk - (size_t)rb * dim_in_1 * azim_num;
         a.row_begin = rb; a.row_end = re;
@@ -897,6 +909,18 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
                                            want_open ? d_open.dev + o : nullptr, st);
             }
             (void)hipEventRecord(e.c, st);
+            if (!rc && to_planes) {
+                // the chunk into its rows of every plane: in place for device planes, through the chunk-planes buffer and one
+                // strided copy (azim_num rows of the chunk's cells, pitch = plane stride) for host planes
+                const size_t cc = (size_t)(re - rb) * dim_in_1, c0 = plane_cell0 + (size_t)(rb - row_begin) * dim_in_1;
+                if (planes_on_dev) rc = hori_to_planes_launch(hori_chunk, cc, azim_num, hori_planes, plane_stride, c0, st);
+                else {
+                    rc = hori_to_planes_launch(hori_chunk, cc, azim_num, (float *)tmp_planes, cc, 0, st);
+                    if (!rc && hipMemcpy2DAsync(hori_planes + c0, plane_stride * sizeof(float), tmp_planes, cc * sizeof(float),
+                                                cc * sizeof(float), (size_t)azim_num, hipMemcpyDeviceToHost, st) != hipSuccess)
+                        rc = set_error(HZ_ERR_HIP, "copy of the horizon planes failed: %s", hipGetErrorString(hipGetLastError()));
+                }
+            }
             if (!rc && stream_out && n_chunk >= 1) rc = copy_out(n_chunk - 1);
             if (rc) return fail(rc);
             unsigned long long c[HZ_CNT_N];
@@ -1149,6 +1173,27 @@ int hz_horizon_gridded_scene_ex(const hz_scene *scene, const float *vec_norm, co
                        elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, stats);
 }
 
+// hori_planes f32[azim_num][rows][dim_in_1] in place of hori_buffer: the checks that need no device, before a scene is built
+static int check_planes_call(const float *hori_planes, int dim_in_0, int dim_in_1, int azim_num, const hz_opts *opts) {
+    if (!hori_planes) return set_error(HZ_ERR_ARG, "hori_planes is NULL");
+    if (dim_in_0 <= 0 || dim_in_1 <= 0 || azim_num <= 0) return set_error(HZ_ERR_ARG, "dim_in_0, dim_in_1 and azim_num must be positive");
+    if (opts && opts->skip_hori) return set_error(HZ_ERR_ARG, "skip_hori with hori_planes: there is nothing to lay out");
+    return HZ_OK;
+}
+
+int hz_horizon_gridded_scene_planes(const hz_scene *scene, const float *vec_norm, const float *vec_north,
+                                    int offset_0, int offset_1, float *hori_planes, int dim_in_0, int dim_in_1,
+                                    int azim_num, float dist_search, float hori_acc, const char *ray_algorithm,
+                                    float elev_ang_low_lim, const uint8_t *mask, float hori_fill,
+                                    float ray_org_elev, const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    if (!scene) return set_error(HZ_ERR_ARG, "scene is NULL");
+    const int rc = check_planes_call(hori_planes, dim_in_0, dim_in_1, azim_num, opts);
+    if (rc) return rc;
+    return horizon_run(reinterpret_cast<const Scene *>(scene), vec_norm, vec_north, offset_0, offset_1,
+                       nullptr, dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                       elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, stats, hori_planes);
+}
+
 int hz_horizon_gridded_scene(const hz_scene *scene, const float *vec_norm, const float *vec_north,
                              int offset_0, int offset_1, float *hori_buffer, int dim_in_0, int dim_in_1,
                              int azim_num, float dist_search, float hori_acc, const char *ray_algorithm,
@@ -1172,13 +1217,14 @@ int hz_horizon_gridded(const float *vert_grid, int dem_dim_0, int dem_dim_1, con
                                  opts, nullptr, stats);
 }
 
-int hz_horizon_gridded_ex(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
-                          const float *vec_north, int offset_0, int offset_1, float *hori_buffer,
-                          int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
-                          const char *ray_algorithm, const char *geom_type, const float *vert_simp,
-                          int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
-                          float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
-                          const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+// the one-shot call: scene, horizon into hori_buffer or (hori_planes != NULL) into planes, release
+static int gridded_one_shot(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
+                            const float *vec_north, int offset_0, int offset_1, float *hori_buffer, float *hori_planes,
+                            int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                            const char *ray_algorithm, const char *geom_type, const float *vert_simp,
+                            int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
+                            float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
+                            const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
     Timer t; t.start();
     const bool verbose = opts && opts->verbose;
     if (verbose) {   // horizon_comp.cpp:643-645 (the engine named there is Embree)
@@ -1207,9 +1253,14 @@ int hz_horizon_gridded_ex(const float *vert_grid, int dem_dim_0, int dem_dim_1, 
         printf("BVH build time: %g s\n", local.t_bvh_s);
         printf("Total initialisation time: %g s\n", t.stop());
     }
-    rc = hz_horizon_gridded_scene_ex(scene, vec_norm, vec_north, offset_0, offset_1, hori_buffer, dim_in_0,
-                                     dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
-                                     elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
+    if (hori_planes)
+        rc = hz_horizon_gridded_scene_planes(scene, vec_norm, vec_north, offset_0, offset_1, hori_planes, dim_in_0,
+                                             dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                                             elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
+    else
+        rc = hz_horizon_gridded_scene_ex(scene, vec_norm, vec_north, offset_0, offset_1, hori_buffer, dim_in_0,
+                                         dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                                         elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
     hz_scene_destroy(scene);   // the reference also releases the scene per call, horizon_comp.cpp:813-814
     local.t_total_s = t.stop();
     if (verbose) {   // :818-820
@@ -1219,6 +1270,34 @@ int hz_horizon_gridded_ex(const float *vert_grid, int dem_dim_0, int dem_dim_1, 
     }
     if (stats) *stats = local;
     return rc;
+}
+
+int hz_horizon_gridded_ex(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
+                          const float *vec_north, int offset_0, int offset_1, float *hori_buffer,
+                          int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                          const char *ray_algorithm, const char *geom_type, const float *vert_simp,
+                          int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
+                          float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
+                          const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    return gridded_one_shot(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north, offset_0, offset_1, hori_buffer, nullptr,
+                            dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm, geom_type, vert_simp,
+                            num_vert_simp, tri_ind_simp, num_tri_simp, elev_ang_low_lim, mask, hori_fill, ray_org_elev,
+                            opts, topo, stats);
+}
+
+int hz_horizon_gridded_planes(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
+                              const float *vec_north, int offset_0, int offset_1, float *hori_planes,
+                              int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                              const char *ray_algorithm, const char *geom_type, const float *vert_simp,
+                              int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
+                              float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
+                              const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    const int rc = check_planes_call(hori_planes, dim_in_0, dim_in_1, azim_num, opts);
+    if (rc) return rc;
+    return gridded_one_shot(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north, offset_0, offset_1, nullptr, hori_planes,
+                            dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm, geom_type, vert_simp,
+                            num_vert_simp, tri_ind_simp, num_tri_simp, elev_ang_low_lim, mask, hori_fill, ray_org_elev,
+                            opts, topo, stats);
 }
 
 int hz_horizon_locations_scene(const hz_scene *scene, const float *coords, const float *vec_norm,
@@ -1331,6 +1410,127 @@ int hz_topo_params(const float *azim, const float *hori, const float *vec_tilt, 
 }
 
 // ---------------------------------------------------------------------------------------
+// the azimuth-major layout (hz_planes.hip): planes[k][y][x] and hori[y][x][k] hold the same 32-bit word
+// ---------------------------------------------------------------------------------------
+// Cells per staging chunk of the entry points below when a side is host memory (and rows of hz_topo_params_planes'
+// cell-major buffer): 256 MiB of horizon, so the device never holds a second full copy.  hz_debug_set("planes_chunk", n).
+static std::atomic<int> g_planes_chunk{0};
+static size_t planes_chunk_cells(size_t cells, int azim_num) {
+    const int knob = g_planes_chunk.load(std::memory_order_relaxed);
+    size_t n = knob > 0 ? (size_t)knob : std::max<size_t>(64, (((size_t)256 << 20) / ((size_t)azim_num * sizeof(float))) & ~(size_t)63);
+    return std::min(n, cells);
+}
+
+static int planes_check_shape(const void *a, const void *b, int len_0, int len_1, int len_2) {
+    if (!a || !b) return set_error(HZ_ERR_ARG, "NULL argument");
+    if (len_0 <= 0 || len_1 <= 0 || len_2 <= 0) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
+    if ((uint64_t)len_0 * (uint64_t)len_1 > (uint64_t)SIZE_MAX / ((uint64_t)len_2 * sizeof(float)))
+        return set_error(HZ_ERR_ARG, "the horizon is too large");
+    return HZ_OK;
+}
+
+struct DevScratch {
+    void *p = nullptr;
+    ~DevScratch() { if (p) (void)hipFree(p); }
+};
+
+// to_planes: hori -> planes, else planes -> hori; each side host or device memory, a host side goes through chunk buffers
+static int planes_convert(bool to_planes, const float *src, float *dst, int len_0, int len_1, int len_2, int device) {
+    int rc = planes_check_shape(src, dst, len_0, len_1, len_2);
+    if (rc) return rc;
+    if ((rc = select_device(device))) return rc;
+    hipStream_t st = nullptr;
+    const size_t cells = (size_t)len_0 * len_1, A = (size_t)len_2;
+    const float *hori_c = to_planes ? src : nullptr, *planes_c = to_planes ? nullptr : src;
+    float *hori = to_planes ? nullptr : dst, *planes = to_planes ? dst : nullptr;
+    const bool hori_dev = is_device_ptr(to_planes ? (const void *)hori_c : (const void *)hori);
+    const bool planes_dev = is_device_ptr(to_planes ? (const void *)planes : (const void *)planes_c);
+    const size_t chunk = (hori_dev && planes_dev) ? cells : planes_chunk_cells(cells, len_2);
+    DevScratch d_h, d_p;
+    if (!hori_dev) HZ_HIP(hipMalloc(&d_h.p, chunk * A * sizeof(float)));
+    if (!planes_dev) HZ_HIP(hipMalloc(&d_p.p, chunk * A * sizeof(float)));
+    for (size_t c0 = 0; c0 < cells; c0 += chunk) {
+        const size_t n = std::min(chunk, cells - c0);
+        if (to_planes) {
+            const float *h = hori_c + c0 * A;
+            if (!hori_dev) { HZ_HIP(hipMemcpyAsync(d_h.p, h, n * A * sizeof(float), hipMemcpyHostToDevice, st)); h = (const float *)d_h.p; }
+            if (planes_dev) rc = hori_to_planes_launch(h, n, len_2, planes, cells, c0, st);
+            else {
+                rc = hori_to_planes_launch(h, n, len_2, (float *)d_p.p, n, 0, st);
+                if (!rc) HZ_HIP(hipMemcpy2DAsync(planes + c0, cells * sizeof(float), d_p.p, n * sizeof(float), n * sizeof(float), A,
+                                                 hipMemcpyDeviceToHost, st));
+            }
+        } else {
+            float *h = hori_dev ? hori + c0 * A : (float *)d_h.p;
+            if (planes_dev) rc = planes_to_hori_launch(planes_c, cells, c0, n, len_2, h, st);
+            else {
+                HZ_HIP(hipMemcpy2DAsync(d_p.p, n * sizeof(float), planes_c + c0, cells * sizeof(float), n * sizeof(float), A,
+                                        hipMemcpyHostToDevice, st));
+                rc = planes_to_hori_launch((const float *)d_p.p, n, 0, n, len_2, h, st);
+            }
+            if (!rc && !hori_dev) HZ_HIP(hipMemcpyAsync(hori + c0 * A, h, n * A * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HZ_HIP(hipStreamSynchronize(st));           // the chunk buffers are used again
+    }
+    return HZ_OK;
+}
+
+int hz_hori_to_planes(const float *hori, int len_0, int len_1, int len_2, float *planes, int device) {
+    return planes_convert(true, hori, planes, len_0, len_1, len_2, device);
+}
+
+int hz_hori_from_planes(const float *planes, int len_0, int len_1, int len_2, float *hori, int device) {
+    return planes_convert(false, planes, hori, len_0, len_1, len_2, device);
+}
+
+// hz_topo_params on planes: rows [rb, re) of every plane back into a bounded cell-major buffer (k_planes_to_hori), then the
+// reduction launch hz_topo_params makes on it -- no numerics are written again, so every map is the same words
+int hz_topo_params_planes(const float *azim, const float *planes, const float *vec_tilt, int len_0, int len_1, int len_2,
+                          float *svf, float *vsf, float *openness, int device) {
+    const bool tilt = svf || vsf;
+    if (!svf && !vsf && !openness) return set_error(HZ_ERR_ARG, "no output requested (svf, vsf and openness are NULL)");
+    if (!azim || !planes || (tilt && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
+    if (len_0 <= 0 || len_1 <= 0 || len_2 < (tilt ? 2 : 1)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
+    int rc = planes_check_shape(azim, planes, len_0, len_1, len_2);
+    if (rc) return rc;
+    if ((rc = select_device(device))) return rc;
+    hipStream_t st = nullptr;
+    const size_t ncell = (size_t)len_0 * len_1, A = (size_t)len_2;
+    DevIn<float> d_azim, d_tilt;
+    DevOut<float> d_svf, d_vsf, d_open;
+    if ((rc = d_azim.bind(azim, A, st))) return rc;
+    if (tilt) if ((rc = d_tilt.bind(vec_tilt, ncell * 3, st))) return rc;
+    if ((rc = d_svf.bind(svf, svf ? ncell : 0))) return rc;
+    if ((rc = d_vsf.bind(vsf, vsf ? ncell : 0))) return rc;
+    if ((rc = d_open.bind(openness, openness ? ncell : 0))) return rc;
+    const bool planes_dev = is_device_ptr(planes);
+    const int rows = (int)std::max<size_t>(1, planes_chunk_cells(ncell, len_2) / (size_t)len_1);
+    const size_t chunk = (size_t)rows * len_1;
+    DevScratch d_h, d_p;
+    HZ_HIP(hipMalloc(&d_h.p, chunk * A * sizeof(float)));
+    if (!planes_dev) HZ_HIP(hipMalloc(&d_p.p, chunk * A * sizeof(float)));
+    for (int rb = 0; rb < len_0; rb += rows) {
+        const int re = std::min(rb + rows, len_0);
+        const size_t c0 = (size_t)rb * len_1, n = (size_t)(re - rb) * len_1;
+        if (planes_dev) rc = planes_to_hori_launch(planes, ncell, c0, n, len_2, (float *)d_h.p, st);
+        else {
+            HZ_HIP(hipMemcpy2DAsync(d_p.p, n * sizeof(float), planes + c0, ncell * sizeof(float), n * sizeof(float), A,
+                                    hipMemcpyHostToDevice, st));
+            rc = planes_to_hori_launch((const float *)d_p.p, n, 0, n, len_2, (float *)d_h.p, st);
+        }
+        if (!rc) rc = topo_multi_launch(d_azim.dev, (const float *)d_h.p, d_tilt.dev ? d_tilt.dev + 3 * c0 : nullptr, re - rb, len_1,
+                                        len_2, d_svf.dev ? d_svf.dev + c0 : nullptr, d_vsf.dev ? d_vsf.dev + c0 : nullptr,
+                                        d_open.dev ? d_open.dev + c0 : nullptr, st);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HZ_HIP(hipStreamSynchronize(st));           // the chunk buffers are used again
+    }
+    if ((rc = d_svf.finish(st)) || (rc = d_vsf.finish(st)) || (rc = d_open.finish(st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    return HZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // test hooks for the build primitives (hz_sort.hip)
 // ---------------------------------------------------------------------------------------
 int hz_debug_sort_pairs(uint32_t *keys, uint32_t *vals, size_t n, int device) {
@@ -1386,6 +1586,7 @@ int hz_debug_set(const char *key, int value) {
     else if (!strcmp(key, "accum_chunk")) hz::g_accum_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "coarse_tile")) hz::g_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_chunk")) hz::g_horisun_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "planes_chunk")) g_planes_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
 }
@@ -1771,11 +1972,6 @@ int hz_terrain_sw_dir_cor_batch(hz_terrain *terrain, const float *sun_positions,
 #endif
 #define HZ_ACCUM_CHUNK_MAX 256      // small grids: 256 positions per chunk are already one large launch
 
-struct DevScratch {
-    void *p = nullptr;
-    ~DevScratch() { if (p) (void)hipFree(p); }
-};
-
 int hz_terrain_accumulate(hz_terrain *terrain, const float *sun_positions, const float *weights, int num_sun,
                           float *sw_dir_cor_sum, float *sunlit_sum, hz_stats *stats) {
     Terrain *t = reinterpret_cast<Terrain *>(terrain);
@@ -1984,6 +2180,7 @@ struct HorizonTerrain {
     std::mutex run_mu;                        // calls on one handle run one after the other (they share the stream)
     const float *hori = nullptr;              // device; borrowed when the caller gave a device pointer
     bool own_hori = false;
+    bool planes = false;                      // hori is f32[azim_num][cells] (hz_horizon_terrain_initialise_planes)
     int azim_num = 0, dim_in_0 = 0, dim_in_1 = 0;
     void *vert = nullptr, *tilt = nullptr, *norm = nullptr, *north = nullptr, *enl = nullptr, *mask = nullptr;   // owned copies
     float fill = 0, ang_max = 89.0f;
@@ -2019,11 +2216,11 @@ int hz_horizon_terrain_create(int device, hz_horizon_terrain **terrain) {
     return HZ_OK;
 }
 
-int hz_horizon_terrain_initialise(hz_horizon_terrain *terrain, const float *hori, int azim_num, const float *vert_grid,
-                                  int dem_dim_0, int dem_dim_1, int offset_0, int offset_1, const float *vec_tilt,
-                                  const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
-                                  const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
-                                  hz_stats *stats) {
+static int horisun_initialise(hz_horizon_terrain *terrain, bool planes, const float *hori, int azim_num, const float *vert_grid,
+                              int dem_dim_0, int dem_dim_1, int offset_0, int offset_1, const float *vec_tilt,
+                              const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
+                              const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
+                              hz_stats *stats) {
     HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
     if (!t) return set_error(HZ_ERR_ARG, "terrain is NULL");
     if (!hori || !vert_grid || !vec_tilt || !vec_norm || !vec_north || !surf_enl_fac || !mask)
@@ -2069,7 +2266,7 @@ int hz_horizon_terrain_initialise(hz_horizon_terrain *terrain, const float *hori
         if (e != hipSuccess) rc = set_error(HZ_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
     }
     if (rc) { horisun_release(t); return rc; }
-    t->azim_num = azim_num; t->dim_in_0 = dim_in_0; t->dim_in_1 = dim_in_1;
+    t->azim_num = azim_num; t->dim_in_0 = dim_in_0; t->dim_in_1 = dim_in_1; t->planes = planes;
     t->fill = sw_dir_cor_fill; t->ang_max = ang_max;
     t->initialised = true;
     if (stats) {
@@ -2078,6 +2275,24 @@ int hz_horizon_terrain_initialise(hz_horizon_terrain *terrain, const float *hori
         stats->num_cells = nc;
     }
     return HZ_OK;
+}
+
+int hz_horizon_terrain_initialise(hz_horizon_terrain *terrain, const float *hori, int azim_num, const float *vert_grid,
+                                  int dem_dim_0, int dem_dim_1, int offset_0, int offset_1, const float *vec_tilt,
+                                  const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
+                                  const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
+                                  hz_stats *stats) {
+    return horisun_initialise(terrain, false, hori, azim_num, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1, vec_tilt,
+                              vec_norm, vec_north, dim_in_0, dim_in_1, surf_enl_fac, mask, sw_dir_cor_fill, ang_max, stats);
+}
+
+int hz_horizon_terrain_initialise_planes(hz_horizon_terrain *terrain, const float *planes, int azim_num, const float *vert_grid,
+                                         int dem_dim_0, int dem_dim_1, int offset_0, int offset_1, const float *vec_tilt,
+                                         const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
+                                         const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
+                                         hz_stats *stats) {
+    return horisun_initialise(terrain, true, planes, azim_num, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1, vec_tilt,
+                              vec_norm, vec_north, dim_in_0, dim_in_1, surf_enl_fac, mask, sw_dir_cor_fill, ang_max, stats);
 }
 
 int hz_horizon_terrain_run(hz_horizon_terrain *terrain, const float *sun_positions, const float *weights, int num_sun,
@@ -2156,7 +2371,8 @@ int hz_horizon_terrain_run(hz_horizon_terrain *terrain, const float *sun_positio
             a.out_u8 = d_u8.dev ? d_u8.dev + nc * (size_t)s0 : nullptr;
             a.out_f32 = d_f32.dev ? d_f32.dev + nc * (size_t)s0 : nullptr;
             a.first = c == 0; a.last = c == plan.num_chunks - 1;
-            if ((rc = horisun_launch(a, plan.blocks, st))) return rc;
+            // planes: the same launch plan, the horizon read as planes[k * cells + c] (k_horisun_planes, hz_planes.hip)
+            if ((rc = t->planes ? horisun_planes_launch(a, nc, plan.blocks, st) : horisun_launch(a, plan.blocks, st))) return rc;
         }
         HZ_HIP(hipEventRecord(e1, st));
         HZ_HIP(hipEventSynchronize(e1));

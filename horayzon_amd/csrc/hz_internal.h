@@ -267,6 +267,17 @@ struct HorisunArgs {
 };
 int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st);
 
+// hz_planes.hip: the azimuth-major horizon layout planes[k][cell] (clause 11; device pointers).
+// Both transpositions move the `cells` x azim_num matrix `hori` (cell-major, contiguous) as 32-bit words; on the plane
+// side cell c of `hori` is element k * plane_stride + cell0 + c, so a chunk of rows goes to its place in every plane of
+// a larger domain (cell0 + cells <= plane_stride).
+int hori_to_planes_launch(const float *hori, size_t cells, int azim_num, float *planes, size_t plane_stride, size_t cell0,
+                          hipStream_t st);
+int planes_to_hori_launch(const float *planes, size_t plane_stride, size_t cell0, size_t cells, int azim_num, float *hori,
+                          hipStream_t st);
+// horisun_launch for a horizon stored as planes: a.hori = planes f32[azim_num][plane_stride] (k_horisun_planes)
+int horisun_planes_launch(const HorisunArgs &a, size_t plane_stride, unsigned blocks, hipStream_t st);
+
 // hz_sort.hip: hand-written stable LSD radix sort (pairs) and exclusive scan, uint32
 size_t sort_temp_elems(size_t n);
 size_t scan_temp_elems(size_t n);

@@ -14,6 +14,7 @@ from . import _validate as V
 from ._lib import Scene, hz_opts, hz_stats, hz_topo_out, ptr
 
 TOPO_NAMES = ("svf", "vsf", "openness")     # the reductions `topo=` can ask for (hz_opts.svf, hz_topo_out.vsf / .openness)
+LAYOUTS = ("cell_major", "azim_major")      # hori (y, x, azim) as the reference has it, or planes (azim, y, x)
 last_stats = None   # hz_stats of the most recent call as a dict (timers, ray count)
 # test hook: defaults of the launch-schedule options ("left_min", "persist_grid", "left_cap_test": hz_opts) for calls that do not
 # pass them -- lets the parity tests run their cases under other schedules without touching every call
@@ -31,6 +32,58 @@ def _check_f32(a, ndim, name):
         raise ValueError("Buffer dtype mismatch, expected 'float32_t' but got '%s'" % a.dtype.name)
 
 
+def check_layout(layout):
+    """``layout=`` of the functions that write or read a horizon: one of ``LAYOUTS``."""
+    if not isinstance(layout, str) or layout not in LAYOUTS:
+        raise ValueError("unknown 'layout': %r (choose from %r)" % (layout, LAYOUTS))
+    return layout == "azim_major"
+
+
+def _convert(hori, to_planes, device):
+    name = "hori" if to_planes else "planes"
+    tensor = not isinstance(hori, np.ndarray) and hasattr(hori, "data_ptr")
+    if not isinstance(hori, np.ndarray) and not tensor:
+        raise TypeError("Argument '%s' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
+                        % (name, type(hori).__name__))
+    ndim = hori.dim() if tensor else hori.ndim
+    if ndim != 3:
+        raise ValueError("Buffer has wrong number of dimensions (expected 3, got %d)" % ndim)
+    if str(hori.dtype).split(".")[-1] != "float32":
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t' but got '%s'" % str(hori.dtype).split(".")[-1])
+    if min(hori.shape) < 1:
+        raise ValueError("Inconsistent/incorrect shape of '%s'" % name)
+    if not (hori.is_contiguous() if tensor else hori.flags["C_CONTIGUOUS"]):
+        raise ValueError("array '%s' is not C-contiguous" % name)
+    if to_planes:
+        (y, x, a), shape = hori.shape, (hori.shape[2], hori.shape[0], hori.shape[1])
+    else:
+        (a, y, x), shape = hori.shape, (hori.shape[1], hori.shape[2], hori.shape[0])
+    if tensor:
+        import torch
+        if hori.device.type != "cuda":
+            raise ValueError("tensor '%s' is not on a GPU" % name)
+        device = hori.device.index
+        out = torch.empty(shape, dtype=torch.float32, device=hori.device)
+        torch.cuda.synchronize(hori.device)       # the library works on a stream of its own
+    else:
+        out = np.empty(shape, dtype=np.float32)
+    L = _lib.lib()
+    _lib.check((L.hz_hori_to_planes if to_planes else L.hz_hori_from_planes)(ptr(hori), y, x, a, ptr(out), device))
+    return out
+
+
+def to_azim_major(hori, *, device=0):
+    """``hori`` float32 (y, x, azim) -> planes float32 (azim, y, x), transposed on the GPU word for word (NaN payloads
+    included).  A NumPy array gives a NumPy array (staged through the GPU ``device`` in bounded chunks); a torch tensor on a
+    GPU gives a torch tensor on that GPU.  The input must be C-contiguous."""
+    return _convert(hori, True, device)
+
+
+def to_cell_major(planes, *, device=0):
+    """The inverse of ``to_azim_major``: planes float32 (azim, y, x) -> ``hori`` float32 (y, x, azim)."""
+    return _convert(planes, False, device)
+
+
 def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     offset_0, offset_1, dist_search, azim_num=360, hori_acc=0.25,
                     ray_algorithm="guess_constant", geom_type="grid",
@@ -40,7 +93,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     num_tri_simp=1, elev_ang_low_lim=-15.0, mask=None,
                     hori_fill=0.0, ray_org_elev=0.01, *, device=0, verbose=False,
                     scene=None, svf_vec_tilt=None, svf_only=False, rows=None, count_work=False, devices=None,
-                    topo=None, topo_vec_tilt=None, topo_only=False,
+                    topo=None, topo_vec_tilt=None, topo_only=False, layout="cell_major",
                     _top_nodes=-1, _regroup=-1, _hit_cache=True, _chunk_rows=0, _near_skip=True, _level_stack=False,
                     _verify_near=False, _left_min=0, _persist_grid=0):
     """Horizon computation for gridded domain.
@@ -66,7 +119,11 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     launch per horizon chunk, and returned as a third value ``{name: float32 (y, x)}``; "svf" and
     "vsf" need ``topo_vec_tilt``, the tilted normals; with ``topo_only`` the horizon is never
     materialised and ``None`` is returned in its place; each map is bit-identical to the
-    ``topo_param`` function applied to the returned horizon).
+    ``topo_param`` function applied to the returned horizon), ``layout`` ("cell_major": the reference's
+    (y, x, azim_num); "azim_major": the returned horizon is float32 (azim_num, y, x), the planes
+    ``to_azim_major`` makes of the cell-major result, word for word -- the layout ``HorizonTerrain`` reads
+    fastest; the cell-major array is never materialised, every other argument keeps its meaning, and
+    ``svf_only`` / ``topo_only`` are refused: there is nothing to lay out).
     """
     global last_stats
     _check_f32(vert_grid, 1, "vert_grid")
@@ -120,6 +177,10 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
          lambda: topo_vec_tilt is not None and topo_vec_tilt.shape != vec_norm.shape),
     ))
 
+    planes = check_layout(layout)
+    if planes and (svf_only or topo_only):
+        raise ValueError("'svf_only' / 'topo_only' cannot be combined with layout=\"azim_major\": there is no horizon to lay out")
+
     # Ensure that passed arrays are contiguous in memory (horizon.pyx:159-163)
     vert_grid = np.ascontiguousarray(vert_grid)
     vec_norm = np.ascontiguousarray(vec_norm)
@@ -132,7 +193,8 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     # Allocate horizon array (horizon.pyx:170-173)
     if svf_only and svf_vec_tilt is None:
         raise ValueError("'svf_only' needs 'svf_vec_tilt'")
-    hori_buffer = None if (svf_only or topo_only) else np.empty((dim_in_0, dim_in_1, azim_num), dtype=np.float32)
+    hori_shape = (azim_num, dim_in_0, dim_in_1) if planes else (dim_in_0, dim_in_1, azim_num)
+    hori_buffer = None if (svf_only or topo_only) else np.empty(hori_shape, dtype=np.float32)
     if rows is not None and hori_buffer is not None:
         hori_buffer.fill(np.nan)   # only a slab is written; every cell is written otherwise
                                    # (masked ones get hori_fill), so the 18 GB pre-fill is skipped
@@ -190,8 +252,10 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     def run(o, st):
         # (the _ex entry points only when hz_topo_out has a map: every other call reaches the library as before)
         ex = () if topo_out is None else (C.byref(topo_out),)
+        if planes:                                # (the planes forms always take the `topo` argument)
+            ex = ex or (None,)
         if scene is None:
-            return (L.hz_horizon_gridded_ex if ex else L.hz_horizon_gridded)(
+            return (L.hz_horizon_gridded_planes if planes else L.hz_horizon_gridded_ex if ex else L.hz_horizon_gridded)(
                 ptr(vert_grid), dem_dim_0, dem_dim_1, ptr(vec_norm), ptr(vec_north),
                 offset_0, offset_1, ptr(hori_buffer), dim_in_0, dim_in_1, azim_num,
                 dist_search, hori_acc, ray_algorithm.encode("utf-8"),
@@ -199,7 +263,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                 ptr(tri_ind_simp), num_tri_simp, elev_ang_low_lim, ptr(mask),
                 hori_fill, ray_org_elev, C.byref(o), *ex, C.byref(st))
         o.device = scene.device
-        return (L.hz_horizon_gridded_scene_ex if ex else L.hz_horizon_gridded_scene)(
+        return (L.hz_horizon_gridded_scene_planes if planes else L.hz_horizon_gridded_scene_ex if ex else L.hz_horizon_gridded_scene)(
             scene._h, ptr(vec_norm), ptr(vec_north), offset_0, offset_1,
             ptr(hori_buffer), dim_in_0, dim_in_1, azim_num, dist_search, hori_acc,
             ray_algorithm.encode("utf-8"), elev_ang_low_lim, ptr(mask), hori_fill,

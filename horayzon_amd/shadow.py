@@ -355,6 +355,22 @@ class HorizonTerrain:
         per-cell arrays of ``Terrain.initialise`` plus ``vec_north``.  ``hori`` is a NumPy array (copied to the GPU) or a
         torch tensor on the object's GPU (borrowed: the object holds a reference, the data must not change while it is in
         use); the other arrays are NumPy and are copied.  No atmospheric refraction (no ``refrac_cor`` / ``elevation``)."""
+        self._initialise(False, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                         vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max)
+
+    def initialise_azim_major(self, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                              vec_tilt, vec_norm, vec_north, surf_enl_fac, mask,
+                              sw_dir_cor_fill=np.nan, ang_max=89.0):
+        """``initialise`` with the horizon in the azimuth-major layout: ``hori`` f32 (azim_num, y, x), what
+        ``horizon_gridded(layout="azim_major")`` returns or ``horizon.to_azim_major`` makes of a cell-major horizon (NumPy:
+        copied; torch tensor on the object's GPU: borrowed).  Every other argument and every check is ``initialise``'s,
+        and so is every result of the methods, bit for bit; a wave's look-up is two loads of consecutive words per position
+        instead of one line per lane.  (A method of its own: ``initialise`` keeps exactly ``Terrain``-style arguments.)"""
+        self._initialise(True, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                         vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max)
+
+    def _initialise(self, planes, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                    vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max):
         _typed(azim, np.float32, 1, "azim")
         self._typed_hori(hori)
         _typed(vert_grid, np.float32, 1, "vert_grid")
@@ -365,6 +381,7 @@ class HorizonTerrain:
         _typed(mask, np.uint8, 2, "mask")
 
         vectors = (vec_tilt, vec_norm, vec_north)
+        cells, num = (tuple(hori.shape[1:]), hori.shape[0]) if planes else (tuple(hori.shape[:2]), hori.shape[2])
         host = [a for a in (azim, hori, vert_grid, vec_tilt, vec_norm, vec_north, surf_enl_fac, mask) if not _is_tensor(a)]
         V.run((
             (ValueError, "inconsistency between input arguments 'vert_grid', 'dem_dim_0' and 'dem_dim_1'",
@@ -376,9 +393,9 @@ class HorizonTerrain:
             (ValueError, "Inconsistent/incorrect shape of 'surf_enl_fac' and/or 'mask'",
              lambda: not V.same_leading_shape((vec_tilt[..., 0], surf_enl_fac, mask), 2, 2)),
             (ValueError, "Inconsistent/incorrect shape of 'hori'",
-             lambda: tuple(hori.shape[:2]) != vec_tilt.shape[:2] or hori.shape[2] < 1),
+             lambda: cells != vec_tilt.shape[:2] or num < 1),
             (ValueError, "'azim' is not the azimuth array of horizon_gridded",
-             lambda: azim.shape[0] != hori.shape[2] or not np.array_equal(azim, gridded_azimuths(hori.shape[2]))),
+             lambda: azim.shape[0] != num or not np.array_equal(azim, gridded_azimuths(num))),
             (ValueError, "not all input arrays are C-contiguous",
              lambda: not all(a.flags["C_CONTIGUOUS"] for a in host) or (_is_tensor(hori) and not hori.is_contiguous())),
             (ValueError, "Vectors in 'vec_tilt', 'vec_norm' and/or 'vec_north' are not normalised",
@@ -389,8 +406,9 @@ class HorizonTerrain:
 
         st = hz_stats()
         self._shape = None
-        _lib.check(_lib.lib().hz_horizon_terrain_initialise(
-            self._h, ptr(hori), hori.shape[2], ptr(vert_grid), dem_dim_0, dem_dim_1, offset_0, offset_1,
+        L = _lib.lib()
+        _lib.check((L.hz_horizon_terrain_initialise_planes if planes else L.hz_horizon_terrain_initialise)(
+            self._h, ptr(hori), num, ptr(vert_grid), dem_dim_0, dem_dim_1, offset_0, offset_1,
             ptr(vec_tilt), ptr(vec_norm), ptr(vec_north), vec_tilt.shape[0], vec_tilt.shape[1],
             ptr(surf_enl_fac), ptr(mask), sw_dir_cor_fill, ang_max, C.byref(st)))
         self._hori = hori if _is_tensor(hori) else None      # keep a borrowed horizon alive

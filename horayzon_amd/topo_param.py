@@ -7,14 +7,44 @@ from . import _lib
 from ._lib import ptr
 
 
-def sky_view_factor(azim, hori, vec_tilt, *, device=0):
+def _cell_shape(hori, layout):
+    """(planes?, (y, x), azim_num) of a 3-D horizon in ``layout`` ("cell_major": (y, x, azim); "azim_major": (azim, y, x))."""
+    from .horizon import check_layout
+    planes = check_layout(layout)
+    if not planes:
+        return False, tuple(hori.shape[:2]), hori.shape[2]
+    if hori.ndim != 3:
+        raise ValueError("Inconsistent/incorrect shapes of input arrays")
+    return True, tuple(hori.shape[1:]), hori.shape[0]
+
+
+def _contiguous_planes(hori):
+    # (np.ascontiguousarray of the cell-major path would silently copy 18 GB of planes)
+    if not hori.flags["C_CONTIGUOUS"]:
+        raise ValueError("array 'hori' is not C-contiguous")
+    return hori
+
+
+def _one_from_planes(kind, azim, hori, vec_tilt, shape, device):
+    out = np.empty(shape, dtype=np.float32)
+    args = [None, None, None]
+    args[kind] = ptr(out)
+    _lib.check(_lib.lib().hz_topo_params_planes(ptr(azim), ptr(hori), ptr(vec_tilt), shape[0], shape[1], hori.shape[0],
+                                                *args, device))
+    return out
+
+
+def sky_view_factor(azim, hori, vec_tilt, *, device=0, layout="cell_major"):
     """Sky view factor (SVF) computation.
 
     Same arguments, checks and result as the reference
     (topo_param.pyx:377-409): azim float32 (azim), hori float32 (y, x, azim)
-    [radian], vec_tilt float32 (y, x, 3); returns svf float32 (y, x)."""
+    [radian], vec_tilt float32 (y, x, 3); returns svf float32 (y, x).  With
+    ``layout="azim_major"`` (not in the reference) hori is float32 (azim, y, x), C-contiguous; the result is the
+    same, bit for bit."""
+    planes, cells, num = _cell_shape(hori, layout)
     # Check arguments (topo_param.pyx:398-404)
-    if (len(azim) != hori.shape[2]) or (hori.shape[:2] != vec_tilt.shape[:2])\
+    if (len(azim) != num) or (cells != vec_tilt.shape[:2])\
             or (vec_tilt.shape[2] != 3):
         raise ValueError("Inconsistent/incorrect shapes of input arrays")
     if ((azim.dtype != "float32") or (hori.dtype != "float32")
@@ -23,8 +53,10 @@ def sky_view_factor(azim, hori, vec_tilt, *, device=0):
     if len(azim) < 2:   # azim[1] - azim[0] is read (topo_param.pyx:433): out of bounds in the reference
         raise ValueError("Inconsistent/incorrect shapes of input arrays")
     azim = np.ascontiguousarray(azim)
-    hori = np.ascontiguousarray(hori)
     vec_tilt = np.ascontiguousarray(vec_tilt)
+    if planes:
+        return _one_from_planes(0, azim, _contiguous_planes(hori), vec_tilt, cells, device)
+    hori = np.ascontiguousarray(hori)
     svf = np.empty(hori.shape[:2], dtype=np.float32)
     _lib.check(_lib.lib().hz_sky_view_factor(ptr(azim), ptr(hori), ptr(vec_tilt),
                                              hori.shape[0], hori.shape[1], hori.shape[2],
@@ -32,10 +64,11 @@ def sky_view_factor(azim, hori, vec_tilt, *, device=0):
     return svf
 
 
-def visible_sky_fraction(azim, hori, vec_tilt, *, device=0):
+def visible_sky_fraction(azim, hori, vec_tilt, *, device=0, layout="cell_major"):
     """Visible sky fraction (solid angle of the visible sky); arguments, checks and result as the
-    reference (topo_param.pyx:465-496)."""
-    if (len(azim) != hori.shape[2]) or (hori.shape[:2] != vec_tilt.shape[:2])\
+    reference (topo_param.pyx:465-496); ``layout`` as in ``sky_view_factor``."""
+    planes, cells, num = _cell_shape(hori, layout)
+    if (len(azim) != num) or (cells != vec_tilt.shape[:2])\
             or (vec_tilt.shape[2] != 3):
         raise ValueError("Inconsistent/incorrect shapes of input arrays")
     if ((azim.dtype != "float32") or (hori.dtype != "float32")
@@ -44,22 +77,27 @@ def visible_sky_fraction(azim, hori, vec_tilt, *, device=0):
     if len(azim) < 2:   # azim[1] - azim[0] is read (topo_param.pyx:520): out of bounds in the reference
         raise ValueError("Inconsistent/incorrect shapes of input arrays")
     azim = np.ascontiguousarray(azim)
-    hori = np.ascontiguousarray(hori)
     vec_tilt = np.ascontiguousarray(vec_tilt)
+    if planes:
+        return _one_from_planes(1, azim, _contiguous_planes(hori), vec_tilt, cells, device)
+    hori = np.ascontiguousarray(hori)
     vsf = np.empty(hori.shape[:2], dtype=np.float32)
     _lib.check(_lib.lib().hz_visible_sky_fraction(ptr(azim), ptr(hori), ptr(vec_tilt), hori.shape[0],
                                                   hori.shape[1], hori.shape[2], ptr(vsf), device))
     return vsf
 
 
-def topographic_openness(azim, hori, *, device=0):
+def topographic_openness(azim, hori, *, device=0, layout="cell_major"):
     """Positive topographic openness (Yokoyama et al. 2002) [radian]; arguments, checks and result as
-    the reference (topo_param.pyx:548-574)."""
-    if len(azim) != hori.shape[2]:
+    the reference (topo_param.pyx:548-574); ``layout`` as in ``sky_view_factor``."""
+    planes, cells, num = _cell_shape(hori, layout)
+    if len(azim) != num:
         raise ValueError("Inconsistent/incorrect shapes of input arrays")
     if (azim.dtype != "float32") or (hori.dtype != "float32"):
         raise ValueError("Input array(s) has/have incorrect data type(s)")
     azim = np.ascontiguousarray(azim)
+    if planes:
+        return _one_from_planes(2, azim, _contiguous_planes(hori), None, cells, device)
     hori = np.ascontiguousarray(hori)
     top = np.empty(hori.shape[:2], dtype=np.float32)
     _lib.check(_lib.lib().hz_topographic_openness(ptr(azim), ptr(hori), hori.shape[0], hori.shape[1],
@@ -70,12 +108,13 @@ def topographic_openness(azim, hori, *, device=0):
 TOPO_NAMES = ("svf", "vsf", "openness")
 
 
-def topo_parameters(azim, hori, vec_tilt=None, which=TOPO_NAMES, *, device=0):
+def topo_parameters(azim, hori, vec_tilt=None, which=TOPO_NAMES, *, device=0, layout="cell_major"):
     """Any of the three reductions above -- sky view factor ("svf"), visible sky fraction ("vsf"),
     positive topographic openness ("openness") -- from ONE pass over the horizon array
     (hz_topo_params).  Arguments and checks as the single-output functions (topo_param.pyx:398-404,
     :486-492, :565-569); ``vec_tilt`` is needed for "svf" and "vsf" only.  Returns
-    ``{name: float32 (y, x)}``, each map bit-identical to the single-output function's."""
+    ``{name: float32 (y, x)}``, each map bit-identical to the single-output function's.  ``layout="azim_major"``: hori is
+    float32 (azim, y, x), C-contiguous (hz_topo_params_planes); the maps are the same, bit for bit."""
     names = [which] if isinstance(which, str) else list(which)
     if not names:
         raise ValueError("'which' is empty")
@@ -85,9 +124,10 @@ def topo_parameters(azim, hori, vec_tilt=None, which=TOPO_NAMES, *, device=0):
     tilted = "svf" in names or "vsf" in names
     if tilted and vec_tilt is None:
         raise ValueError("'svf' and 'vsf' need 'vec_tilt'")
+    planes, cells, num = _cell_shape(hori, layout)
     # Check arguments (topo_param.pyx:398-404 / :565-569)
     if tilted:
-        if (len(azim) != hori.shape[2]) or (hori.shape[:2] != vec_tilt.shape[:2])\
+        if (len(azim) != num) or (cells != vec_tilt.shape[:2])\
                 or (vec_tilt.shape[2] != 3):
             raise ValueError("Inconsistent/incorrect shapes of input arrays")
         if ((azim.dtype != "float32") or (hori.dtype != "float32")
@@ -97,17 +137,18 @@ def topo_parameters(azim, hori, vec_tilt=None, which=TOPO_NAMES, *, device=0):
             raise ValueError("Inconsistent/incorrect shapes of input arrays")
         vec_tilt = np.ascontiguousarray(vec_tilt)
     else:
-        if len(azim) != hori.shape[2]:
+        if len(azim) != num:
             raise ValueError("Inconsistent/incorrect shapes of input arrays")
         if (azim.dtype != "float32") or (hori.dtype != "float32"):
             raise ValueError("Input array(s) has/have incorrect data type(s)")
         vec_tilt = None
     azim = np.ascontiguousarray(azim)
-    hori = np.ascontiguousarray(hori)
-    out = {n: np.empty(hori.shape[:2], dtype=np.float32) for n in TOPO_NAMES if n in names}
-    _lib.check(_lib.lib().hz_topo_params(ptr(azim), ptr(hori), ptr(vec_tilt), hori.shape[0], hori.shape[1],
-                                         hori.shape[2], ptr(out.get("svf")), ptr(out.get("vsf")),
-                                         ptr(out.get("openness")), device))
+    hori = _contiguous_planes(hori) if planes else np.ascontiguousarray(hori)
+    out = {n: np.empty(cells, dtype=np.float32) for n in TOPO_NAMES if n in names}
+    L = _lib.lib()
+    _lib.check((L.hz_topo_params_planes if planes else L.hz_topo_params)(
+        ptr(azim), ptr(hori), ptr(vec_tilt), cells[0], cells[1], num, ptr(out.get("svf")), ptr(out.get("vsf")),
+        ptr(out.get("openness")), device))
     return out
 
 

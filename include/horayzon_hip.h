@@ -240,6 +240,51 @@ int hz_horizon_gridded_scene_ex(const hz_scene *scene,
                                 float hori_fill, float ray_org_elev,
                                 const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
 
+/* ------------------------------------------------------------------------- */
+/* The azimuth-major layout (additive): planes f32[azim_num][y][x] next to hori f32[y][x][azim_num].            */
+/* planes[k][y][x] and hori[y][x][k] hold the same 32-bit word, NaN payloads and hori_fill included: the         */
+/* functions below move words and decide nothing numerically, so every result obtained through planes is         */
+/* bit-identical to the one obtained through the cell-major layout.  It is the layout a stored horizon is read   */
+/* back in (hz_horizon_terrain_initialise_planes): a wave that looks one azimuth up reads consecutive words.    */
+/* ------------------------------------------------------------------------- */
+/* The _ex forms with `hori_planes` f32[azim_num][rows][dim_in_1] in place of hori_buffer (host or device        */
+/* memory); the cell-major horizon is never written.  Each chunk of rows is traced into the bounded chunk buffer */
+/* of opts->skip_hori, reduced as the _ex forms reduce it (topo, opts->svf), and transposed into its rows of     */
+/* every plane; a host hori_planes receives it through a second chunk buffer and one strided copy.  Row slabs    */
+/* mean what they mean for hori_buffer: rows = dim_in_0 and the planes address inner-domain row 0, or, with      */
+/* opts->hori_is_slab, rows = row_end - row_begin and they address row_begin; rows outside the slab are left     */
+/* untouched.  opts->skip_hori is HZ_ERR_ARG here.  stats->scratch_bytes includes the chunk buffers.             */
+int hz_horizon_gridded_planes(const float *vert_grid, int dem_dim_0, int dem_dim_1,
+                              const float *vec_norm, const float *vec_north,
+                              int offset_0, int offset_1,
+                              float *hori_planes, int dim_in_0, int dim_in_1,
+                              int azim_num, float dist_search, float hori_acc,
+                              const char *ray_algorithm, const char *geom_type,
+                              const float *vert_simp, int num_vert_simp,
+                              const int32_t *tri_ind_simp, int num_tri_simp,
+                              float elev_ang_low_lim, const uint8_t *mask,
+                              float hori_fill, float ray_org_elev,
+                              const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+int hz_horizon_gridded_scene_planes(const hz_scene *scene,
+                                    const float *vec_norm, const float *vec_north,
+                                    int offset_0, int offset_1,
+                                    float *hori_planes, int dim_in_0, int dim_in_1,
+                                    int azim_num, float dist_search, float hori_acc,
+                                    const char *ray_algorithm,
+                                    float elev_ang_low_lim, const uint8_t *mask,
+                                    float hori_fill, float ray_org_elev,
+                                    const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+/* hori f32[len_0][len_1][len_2] <-> planes f32[len_2][len_0][len_1], a tiled transpose on the device.  Each     */
+/* pointer may be host or device memory; a host side is staged in chunks of at most 256 MiB, never as a second   */
+/* full copy on the device.  All lengths >= 1.                                                                   */
+int hz_hori_to_planes(const float *hori, int len_0, int len_1, int len_2, float *planes, int device);
+int hz_hori_from_planes(const float *planes, int len_0, int len_1, int len_2, float *hori, int device);
+/* hz_topo_params with the horizon given as planes f32[len_2][len_0][len_1] (host or device): chunk by chunk    */
+/* the rows go back into a bounded cell-major buffer and through the reduction launch of hz_topo_params, so each */
+/* map is bit-identical to hz_topo_params' (and to the single-output functions').                               */
+int hz_topo_params_planes(const float *azim, const float *planes, const float *vec_tilt, int len_0, int len_1, int len_2,
+                          float *svf, float *vsf, float *openness, int device);
+
 /* Horizon (and optionally distance to the horizon) for arbitrary locations; argument list     */
 /* mirrors horizon_locations_comp (horizon_comp.h:22-34, horizon_comp.cpp:828-1094).           */
 /* coords f32[num_loc][3], vec_norm / vec_north f32[num_loc][3], ray_org_elev f32[num_loc],    */
@@ -304,7 +349,8 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* over the azimuth axis use the one-lane-per-cell fallback kernel, "accum_chunk" = sun positions per chunk of                   */
 /* hz_terrain_accumulate and hz_terrain_sw_dir_cor_coarse (<= 0: the default, from the scratch budget), "coarse_tile" = cells   */
 /* of the LDS tile of hz_terrain_sw_dir_cor_coarse's reduction (<= 0 or above the default: the default; blocks wider than the  */
-/* tile take the kernel without LDS), "horisun_chunk" = sun positions per launch of hz_horizon_terrain_run (<= 0: the default)  */
+/* tile take the kernel without LDS), "horisun_chunk" = sun positions per launch of hz_horizon_terrain_run (<= 0: the default), */
+/* "planes_chunk" = cells per staging chunk of hz_hori_to_planes / _from_planes / hz_topo_params_planes (<= 0: the default)    */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */
@@ -446,6 +492,13 @@ typedef struct hz_horisun_out {
 } hz_horisun_out;
 int hz_horizon_terrain_create(int device, hz_horizon_terrain** t);
 int hz_horizon_terrain_initialise(hz_horizon_terrain* t, const float* hori, int azim_num,
+        const float* vert_grid, int dem_dim_0, int dem_dim_1, int offset_0, int offset_1,
+        const float* vec_tilt, const float* vec_norm, const float* vec_north, int dim_in_0, int dim_in_1,
+        const float* surf_enl_fac, const uint8_t* mask, float sw_dir_cor_fill, float ang_max, hz_stats* stats);
+/* hz_horizon_terrain_initialise with the horizon given as planes f32[azim_num][dim_in_0][dim_in_1] (host:       */
+/* copied; device: borrowed).  hz_horizon_terrain_run then reads hori[k mod A] as planes[k mod A][cell]; the     */
+/* arithmetic, the chunking of positions, the sums and the outputs are the same, and so is every result.         */
+int hz_horizon_terrain_initialise_planes(hz_horizon_terrain* t, const float* planes, int azim_num,
         const float* vert_grid, int dem_dim_0, int dem_dim_1, int offset_0, int offset_1,
         const float* vec_tilt, const float* vec_norm, const float* vec_north, int dim_in_0, int dim_in_1,
         const float* surf_enl_fac, const uint8_t* mask, float sw_dir_cor_fill, float ang_max, hz_stats* stats);
