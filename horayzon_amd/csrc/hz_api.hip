@@ -5,6 +5,7 @@
 // reference's float/double promotion pattern, uploads, kernel launches, reports.
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
+#include "hz_horisun_coarse_plan.h"
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -1586,6 +1587,8 @@ int hz_debug_set(const char *key, int value) {
     else if (!strcmp(key, "accum_chunk")) hz::g_accum_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "coarse_tile")) hz::g_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_chunk")) hz::g_horisun_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "horisun_coarse_tile")) hz::g_horisun_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "horisun_coarse_route")) hz::g_horisun_coarse_route.store(value < 0 ? -1 : (value == 1 ? 1 : 0), std::memory_order_relaxed);
     else if (!strcmp(key, "planes_chunk")) g_planes_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
@@ -2381,6 +2384,103 @@ int hz_horizon_terrain_run(hz_horizon_terrain *terrain, const float *sun_positio
     Timer t_d2h; t_d2h.start();
     if ((rc = d_u8.finish(st))) return rc;
     if ((rc = d_f32.finish(st))) return rc;
+    if ((rc = d_sw.finish(st))) return rc;
+    if ((rc = d_lit.finish(st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    if (stats) {
+        stats->num_cells = nc;
+        stats->t_kernel_s += (double)ms * 1e-3;
+        stats->t_d2h_s += t_d2h.stop();
+        stats->t_total_s += t_total.stop();
+        stats->scratch_bytes = scratch;
+    }
+    return HZ_OK;
+}
+
+// HorizonTerrain.sw_dir_cor_coarse (DESIGN.md section 4 clause 12).  Fused route: k_horisun_coarse (hz_horisun_coarse.hip) per
+// chunk, no map per position.  Two-pass route (the measured default of both layouts, "horisun_coarse_route" = 1, and blocks
+// wider than the fused kernel's LDS tile): the chunk goes through k_horisun / k_horisun_planes into scratch u8[k][cells] / f32[k][cells], which k_coarse_reduce
+// (hz_subgrid.hip) reduces.  Device memory besides the outputs -- the scratch of the two-pass route, the cell counts of the
+// coarse cells, staged positions -- does not depend on num_sun.
+int hz_horizon_terrain_sw_dir_cor_coarse(hz_horizon_terrain *terrain, const float *sun_positions, int num_sun, int pixel_per_gc_0,
+                                         int pixel_per_gc_1, float *f_cor, float *sunlit_frac, hz_stats *stats) {
+    HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "HorizonTerrain is not initialised");
+    if (!sun_positions || num_sun <= 0) return set_error(HZ_ERR_ARG, "array 'sun_positions' has incorrect shape");
+    if (!f_cor && !sunlit_frac) return set_error(HZ_ERR_ARG, "no output buffer (f_cor and sunlit_frac are NULL)");
+    if (f_cor == sunlit_frac) return set_error(HZ_ERR_ARG, "'f_cor' and 'sunlit_frac' must be different arrays");
+    const int p0 = pixel_per_gc_0, p1 = pixel_per_gc_1;
+    if (p0 < 1 || p1 < 1 || p0 > t->dim_in_0 || p1 > t->dim_in_1 || t->dim_in_0 % p0 || t->dim_in_1 % p1)
+        return set_error(HZ_ERR_ARG, "'pixel_per_gc' (%d, %d) must be positive and divide the inner domain (%d, %d)", p0, p1,
+                         t->dim_in_0, t->dim_in_1);
+    const bool want_sw = f_cor != nullptr, want_lit = sunlit_frac != nullptr;
+    HorisunPlan plan;
+    if (horisun_plan(t->dim_in_0, t->dim_in_1, t->azim_num, num_sun, g_horisun_chunk.load(std::memory_order_relaxed), 0, &plan))
+        return set_error(HZ_ERR_ARG, "too many sun positions");
+    const int k = std::min(plan.chunk, HZ_HSC_CHUNK_MAX);        // grid.y of either route
+    HorisunCoarsePlan cp;
+    int rc;
+    if ((rc = horisun_coarse_plan_for(t->dim_in_0, t->dim_in_1, p0, p1, k, t->planes, want_lit, want_sw, &cp))) return rc;
+    const size_t nc = plan.cells;
+    const int gy = t->dim_in_0 / p0, gx = t->dim_in_1 / p1;
+    const size_t ng = (size_t)gy * gx;
+    if (ng > (size_t)SIZE_MAX / sizeof(float) / (size_t)num_sun) return set_error(HZ_ERR_ARG, "too many sun positions");
+    std::lock_guard<std::mutex> run_lock(t->run_mu);
+    HZ_HIP(hipSetDevice(t->device));
+    hipStream_t st = t->stream;
+    Timer t_total; t_total.start();
+    const bool sun_on_dev = is_device_ptr(sun_positions);
+    DevScratch codes, vals, count, stage;
+    size_t scratch = 0;
+    if (cp.fallback) {
+        if (want_lit) { HZ_HIP(hipMalloc(&codes.p, (size_t)k * nc)); scratch += (size_t)k * nc; }
+        if (want_sw) { HZ_HIP(hipMalloc(&vals.p, (size_t)k * nc * 4)); scratch += (size_t)k * nc * 4; }
+    }
+    HZ_HIP(hipMalloc(&count.p, ng * sizeof(unsigned))); scratch += ng * sizeof(unsigned);
+    if (!sun_on_dev) { HZ_HIP(hipMalloc(&stage.p, (size_t)k * 3 * sizeof(float))); scratch += (size_t)k * 3 * sizeof(float); }
+    float *stage_sun = static_cast<float *>(stage.p);           // host positions go up one chunk at a time
+    DevOut<float> d_sw, d_lit;
+    if ((rc = d_sw.bind(f_cor, want_sw ? ng * (size_t)num_sun : 0))) return rc;
+    if ((rc = d_lit.bind(sunlit_frac, want_lit ? ng * (size_t)num_sun : 0))) return rc;
+    HorisunArgs a;
+    a.hori = t->hori; a.vert = (const float *)t->vert;
+    a.vec_tilt = (const float *)t->tilt; a.vec_norm = (const float *)t->norm; a.vec_north = (const float *)t->north;
+    a.surf_enl_fac = (const float *)t->enl; a.mask = (const uint8_t *)t->mask;
+    a.cells = nc; a.azim_num = t->azim_num;
+    a.fill = t->fill; a.dot_prod_min = cosf(deg2rad_f(t->ang_max));            // shadow_comp.cpp:498
+    a.weights = nullptr; a.acc_sw = a.acc_lit = nullptr; a.sum_sw = a.sum_lit = nullptr;
+    a.first = a.last = 1;
+    a.out_u8 = static_cast<uint8_t *>(codes.p);
+    a.out_f32 = static_cast<float *>(vals.p);
+    float ms = 0.0f;
+    {
+        hipEvent_t e0, e1;
+        HZ_HIP(hipEventCreate(&e0)); HZ_HIP(hipEventCreate(&e1));
+        struct EvFree { hipEvent_t a, b; ~EvFree() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_free{e0, e1};
+        HZ_HIP(hipEventRecord(e0, st));
+        const unsigned *n = static_cast<const unsigned *>(count.p);
+        if ((rc = coarse_count_launch(a.mask, t->dim_in_0, t->dim_in_1, p0, p1, static_cast<unsigned *>(count.p), st))) return rc;
+        for (int s0 = 0; s0 < num_sun; s0 += k) {
+            const int kc = std::min(k, num_sun - s0);
+            if (sun_on_dev) a.suns = sun_positions + 3 * (size_t)s0;
+            else {
+                HZ_HIP(hipMemcpyAsync(stage_sun, sun_positions + 3 * (size_t)s0, (size_t)kc * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+                a.suns = stage_sun;
+            }
+            a.num_sun = kc;
+            float *o_sw = d_sw.dev ? d_sw.dev + ng * (size_t)s0 : nullptr, *o_lit = d_lit.dev ? d_lit.dev + ng * (size_t)s0 : nullptr;
+            if (cp.fallback) {
+                if ((rc = t->planes ? horisun_planes_launch(a, nc, plan.blocks, st) : horisun_launch(a, plan.blocks, st))) return rc;
+                if ((rc = coarse_reduce_launch(a.out_u8, a.out_f32, a.mask, n, t->dim_in_0, t->dim_in_1, p0, p1, kc, t->fill,
+                                               o_sw, o_lit, st)))
+                    return rc;
+            } else if ((rc = horisun_coarse_launch(a, t->planes, nc, cp, n, t->dim_in_1, p0, p1, o_sw, o_lit, st))) return rc;
+        }
+        HZ_HIP(hipEventRecord(e1, st));
+        HZ_HIP(hipEventSynchronize(e1));
+        HZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+    }
+    Timer t_d2h; t_d2h.start();
     if ((rc = d_sw.finish(st))) return rc;
     if ((rc = d_lit.finish(st))) return rc;
     HZ_HIP(hipStreamSynchronize(st));

@@ -31,6 +31,8 @@ extern std::atomic<int> g_topo_wide;         // 1: the reductions over the azimu
 extern std::atomic<int> g_accum_chunk;       // > 0: sun positions per chunk of hz_terrain_accumulate (default 0: from the memory budget)
 extern std::atomic<int> g_coarse_tile;       // > 0: cells of k_coarse_reduce's LDS tile, at most the default (hz_subgrid.hip; default 0)
 extern std::atomic<int> g_horisun_chunk;     // > 0: sun positions per launch of hz_horizon_terrain_run (default 0: HZ_HORISUN_CHUNK)
+extern std::atomic<int> g_horisun_coarse_tile;    // > 0: cells of k_horisun_coarse's LDS tile, at most the default (hz_horisun_coarse.hip; default 0)
+extern std::atomic<int> g_horisun_coarse_route;   // hz_horizon_terrain_sw_dir_cor_coarse: 0 the fused kernel, 1 the two-pass route, -1 the layout's default
 
 #define HZ_HIP(expr)                                                                      \
     do {                                                                                  \
@@ -277,6 +279,17 @@ int planes_to_hori_launch(const float *planes, size_t plane_stride, size_t cell0
                           hipStream_t st);
 // horisun_launch for a horizon stored as planes: a.hori = planes f32[azim_num][plane_stride] (k_horisun_planes)
 int horisun_planes_launch(const HorisunArgs &a, size_t plane_stride, unsigned blocks, hipStream_t st);
+
+// hz_horisun_coarse.hip (hz_horizon_terrain_sw_dir_cor_coarse; device pointers): the plan of the fused kernel for chunks of
+// up to `chunk` positions (hz_horisun_coarse_plan.h; plan->fallback = 1: the shape, the "horisun_coarse_route" knob or the layout's default asks
+// for the two-pass route), and one launch of k_horisun_coarse over the a.num_sun <= chunk positions of a chunk: block means
+// f_cor / lit f32[a.num_sun][gy][gx] (null: not wanted; as the plan was made) from a.hori (planes: f32[azim_num][plane_stride]),
+// n = coarse_count_launch's counts.  Of `a` the inputs, cells, azim_num, suns, num_sun, fill and dot_prod_min are read.
+struct HorisunCoarsePlan;
+int horisun_coarse_plan_for(int dim_0, int dim_1, int p0, int p1, int chunk, bool planes, bool codes, bool vals,
+                            HorisunCoarsePlan *plan);
+int horisun_coarse_launch(const HorisunArgs &a, bool planes, size_t plane_stride, const HorisunCoarsePlan &plan,
+                          const unsigned *n, int dim_1, int p0, int p1, float *f_cor, float *lit, hipStream_t st);
 
 // hz_sort.hip: hand-written stable LSD radix sort (pairs) and exclusive scan, uint32
 size_t sort_temp_elems(size_t n);

@@ -516,3 +516,50 @@ class HorizonTerrain:
                 self._check_out(buf, name)
         self._run(sun_positions, weights, sun_positions.shape[0], sw_dir_cor_sum=sw_dir_cor_sum, sunlit_sum=sunlit_sum,
                   shadow=shadow_buffers, sw_dir_cor=sw_dir_cor_buffers)
+
+    _pixel_per_gc = staticmethod(Terrain._pixel_per_gc)
+
+    def sw_dir_cor_coarse(self, sun_positions, pixel_per_gc, *, f_cor=None, sunlit_frac=None):
+        """``Terrain.sw_dir_cor_coarse`` from the horizon (clause 12): per sun position of sun_positions
+        f32[S][3] (S >= 1), means over blocks of P0 x P1 cells of the inner domain (``pixel_per_gc``: an int P or a pair
+        (P0, P1) that divide its shape), without a map per position: ``f_cor[s][I][J]`` = the mean of
+        sw_dir_cor(sun_positions[s]) and ``sunlit_frac[s][I][J]`` = the fraction of cells for which shadow() gives 0, both
+        over the unmasked cells of the block.  The sum is a float64 accumulator over the block's unmasked cells in row-major
+        order, divided by their number in float64 and rounded to float32 once; a block without an unmasked cell gets
+        ``sw_dir_cor_fill``.  Outputs f32[S][gy][gx], NumPy or torch tensors on the object's GPU; at least one.  Both horizon
+        layouts give the same words.  Device memory besides the outputs does not grow with S
+        (``last_stats["scratch_bytes"]``)."""
+        outs = (("f_cor", f_cor), ("sunlit_frac", sunlit_frac))
+        self._accum_arg(sun_positions, 2, "sun_positions")
+        p0, p1 = self._pixel_per_gc(pixel_per_gc)
+        for name, buf in outs:
+            if buf is not None:
+                self._accum_arg(buf, 3, name)
+        if self._shape is None:
+            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
+        given = [buf for _, buf in outs if buf is not None]
+        dim_0, dim_1 = self._shape
+
+        def contiguous(a):
+            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
+
+        def coarse_shape():
+            return (sun_positions.shape[0], dim_0 // p0, dim_1 // p1)
+        V.run((
+            (ValueError, "at least one of 'f_cor' and 'sunlit_frac' must be given", lambda: not given),
+            (ValueError, "array 'sun_positions' has incorrect shape",
+             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
+            (ValueError, "'pixel_per_gc' (%d, %d) must be positive and divide the inner domain (%d, %d)" % (p0, p1, dim_0, dim_1),
+             lambda: p0 < 1 or p1 < 1 or p0 > dim_0 or p1 > dim_1 or dim_0 % p0 != 0 or dim_1 % p1 != 0),
+            (ValueError, "array 'f_cor' has incorrect shape",
+             lambda: f_cor is not None and tuple(f_cor.shape) != coarse_shape()),
+            (ValueError, "array 'sunlit_frac' has incorrect shape",
+             lambda: sunlit_frac is not None and tuple(sunlit_frac.shape) != coarse_shape()),
+            (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in [sun_positions] + given)),
+            (ValueError, "'f_cor' and 'sunlit_frac' must be different arrays",
+             lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
+        ))
+        st = hz_stats()
+        _lib.check(_lib.lib().hz_horizon_terrain_sw_dir_cor_coarse(
+            self._h, ptr(sun_positions), sun_positions.shape[0], p0, p1, ptr(f_cor), ptr(sunlit_frac), C.byref(st)))
+        self.last_stats = st.as_dict()

@@ -350,6 +350,7 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* hz_terrain_accumulate and hz_terrain_sw_dir_cor_coarse (<= 0: the default, from the scratch budget), "coarse_tile" = cells   */
 /* of the LDS tile of hz_terrain_sw_dir_cor_coarse's reduction (<= 0 or above the default: the default; blocks wider than the  */
 /* tile take the kernel without LDS), "horisun_chunk" = sun positions per launch of hz_horizon_terrain_run (<= 0: the default), */
+/* "horisun_coarse_route" / "horisun_coarse_tile": see hz_horizon_terrain_sw_dir_cor_coarse (< 0: the default),                 */
 /* "planes_chunk" = cells per staging chunk of hz_hori_to_planes / _from_planes / hz_topo_params_planes (<= 0: the default)    */
 int hz_debug_set(const char *key, int value);
 
@@ -508,6 +509,27 @@ int hz_horizon_terrain_initialise_planes(hz_horizon_terrain* t, const float* pla
 /* besides per-position maps staged for host outputs; it does not grow with num_sun                             */
 int hz_horizon_terrain_run(hz_horizon_terrain* t, const float* sun_positions, const float* weights /* NULL = ones */,
         int num_sun, const hz_horisun_out* out, hz_stats* stats);
+/* DESIGN.md section 4 clause 12: hz_terrain_sw_dir_cor_coarse from the stored horizon.  For position s and coarse cell       */
+/* (I, J), B = the cells (i, j), I * P0 <= i < (I + 1) * P0, J * P1 <= j < (J + 1) * P1, with mask[i][j] == 1, and n = |B|:     */
+/*   f_cor[s][I][J] = (float)(SUM / (double)n), SUM a float64 accumulator that starts at 0.0 and takes (double)v one cell at a   */
+/*     time over B, i ascending and within a row j ascending, v = bit for bit what hz_horizon_terrain_run writes into           */
+/*     sw_dir_cor for that cell and position (a masked or unlit cell may contribute +0.0 instead of being skipped: the           */
+/*     accumulator is never -0.0, so the add changes no bit);                                                                   */
+/*   sunlit_frac[s][I][J] = (float)((double)n_lit / (double)n), n_lit = the cells of B whose shadow code is 0;                   */
+/*   n == 0: both are sw_dir_cor_fill.  No atmospheric refraction.                                                              */
+/* pixel_per_gc_0 / _1 >= 1 and divisors of dim_in_0 / dim_in_1; f_cor, sunlit_frac f32[num_sun][gy][gx], NULL = not wanted (at */
+/* least one; they must differ); positions and outputs host or device pointers.  The look-up is evaluated for the cells with    */
+/* dot_ts > 0 if sunlit_frac is wanted (it serves both outputs), else for dot_ts > dot_prod_min.  Both horizon layouts give the */
+/* same words.  Positions go in chunks ("horisun_chunk").  Two routes, chosen by hz_debug_set("horisun_coarse_route", r):       */
+/* r = 1, two passes per chunk: the look-up kernel of hz_horizon_terrain_run into scratch maps (5 B per cell and position of   */
+/* the chunk), then hz_terrain_sw_dir_cor_coarse's reduction, which obeys "coarse_tile"; r = 0, one fused kernel per chunk, no  */
+/* map per position; blocks wider than its LDS tile ("horisun_coarse_tile" cells, <= 0 or above the default of 4096: the         */
+/* default) go the two-pass route.  r < 0 (the default): the route measured as the faster one for the layout, at present the     */
+/* two-pass route for both.  stats as                                                                      */
+/* hz_horizon_terrain_run; scratch_bytes = device memory besides the outputs and their staging, it does not grow with num_sun   */
+int hz_horizon_terrain_sw_dir_cor_coarse(hz_horizon_terrain *t, const float *sun_positions, int num_sun,
+                                         int pixel_per_gc_0, int pixel_per_gc_1,
+                                         float *f_cor, float *sunlit_frac, hz_stats *stats);
 int hz_horizon_terrain_destroy(hz_horizon_terrain* t);
 
 /* ------------------------------------------------------------------------- */
