@@ -89,7 +89,7 @@ SYMBOLS = (
     "hz_horizon_terrain_create", "hz_horizon_terrain_initialise", "hz_horizon_terrain_run", "hz_horizon_terrain_destroy",
     "hz_horizon_gridded_planes", "hz_horizon_gridded_scene_planes", "hz_hori_to_planes", "hz_hori_from_planes",
     "hz_topo_params_planes", "hz_horizon_terrain_initialise_planes",
-    "hz_horizon_terrain_sw_dir_cor_coarse",
+    "hz_horizon_terrain_sw_dir_cor_coarse", "hz_horizon_terrain_refraction",
 )
 
 
@@ -202,6 +202,7 @@ def lib():
     L.hz_horizon_terrain_initialise_planes.argtypes = L.hz_horizon_terrain_initialise.argtypes
     L.hz_horizon_terrain_run.argtypes = [vp, vp, vp, ip, C.POINTER(hz_horisun_out), C.POINTER(hz_stats)]
     L.hz_horizon_terrain_sw_dir_cor_coarse.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.POINTER(hz_stats)]
+    L.hz_horizon_terrain_refraction.argtypes = [vp, vp, C.POINTER(hz_stats)]
     L.hz_horizon_terrain_destroy.argtypes = [vp]
     for name in SYMBOLS:
         if name not in ("hz_last_error", "hz_vert_grid_len"):

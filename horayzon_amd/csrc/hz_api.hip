@@ -2187,6 +2187,7 @@ struct HorizonTerrain {
     int azim_num = 0, dim_in_0 = 0, dim_in_1 = 0;
     void *vert = nullptr, *tilt = nullptr, *norm = nullptr, *north = nullptr, *enl = nullptr, *mask = nullptr;   // owned copies
     float fill = 0, ang_max = 89.0f;
+    double *refrac_fac = nullptr;             // hz_horizon_terrain_refraction: per cell the factor of the refraction formula (k_refrac_factor), or null = off
     bool initialised = false;
 };
 
@@ -2198,6 +2199,7 @@ static void horisun_release(HorizonTerrain *t) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
+    if (t->refrac_fac) { (void)hipFree(t->refrac_fac); t->refrac_fac = nullptr; }
     t->hori = nullptr; t->own_hori = false; t->initialised = false;
 }
 
@@ -2298,6 +2300,36 @@ int hz_horizon_terrain_initialise_planes(hz_horizon_terrain *terrain, const floa
                               vec_norm, vec_north, dim_in_0, dim_in_1, surf_enl_fac, mask, sw_dir_cor_fill, ang_max, stats);
 }
 
+// Refraction on (elevation f32[cells], host or device: copied, as surf_enl_fac is) or off (NULL): the per-cell float64 factor of
+// Terrain's refrac_cor, 8 bytes per cell, which every later call hands to its kernels (clause 13)
+int hz_horizon_terrain_refraction(hz_horizon_terrain *terrain, const float *elevation, hz_stats *stats) {
+    HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "HorizonTerrain is not initialised");
+    std::lock_guard<std::mutex> run_lock(t->run_mu);
+    HZ_HIP(hipSetDevice(t->device));
+    hipStream_t st = t->stream;
+    Timer t_total; t_total.start();
+    HZ_HIP(hipStreamSynchronize(st));
+    if (t->refrac_fac) { (void)hipFree(t->refrac_fac); t->refrac_fac = nullptr; }
+    const size_t nc = (size_t)t->dim_in_0 * (size_t)t->dim_in_1;
+    if (elevation) {
+        DevScratch elev, fac;
+        int rc;
+        if ((rc = horisun_copy(elevation, nc * sizeof(float), st, &elev.p))) return rc;
+        HZ_HIP(hipMalloc(&fac.p, nc * sizeof(double)));
+        if ((rc = shadow_refrac_factor(static_cast<const float *>(elev.p), nc, static_cast<double *>(fac.p), st))) return rc;
+        HZ_HIP(hipStreamSynchronize(st));
+        t->refrac_fac = static_cast<double *>(fac.p);
+        fac.p = nullptr;
+    }
+    if (stats) {
+        const double dt = t_total.stop();
+        stats->t_h2d_s += dt; stats->t_total_s += dt;
+        stats->num_cells = nc;
+    }
+    return HZ_OK;
+}
+
 int hz_horizon_terrain_run(hz_horizon_terrain *terrain, const float *sun_positions, const float *weights, int num_sun,
                            const hz_horisun_out *out, hz_stats *stats) {
     HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
@@ -2347,6 +2379,7 @@ int hz_horizon_terrain_run(hz_horizon_terrain *terrain, const float *sun_positio
     a.surf_enl_fac = (const float *)t->enl; a.mask = (const uint8_t *)t->mask;
     a.cells = nc; a.azim_num = t->azim_num;
     a.fill = t->fill; a.dot_prod_min = cosf(deg2rad_f(t->ang_max));            // shadow_comp.cpp:498
+    a.refrac_fac = t->refrac_fac;
     a.acc_sw = out->sw_dir_cor_sum ? static_cast<double *>(acc.p) : nullptr;
     a.acc_lit = out->sunlit_sum ? static_cast<double *>(acc.p) + (out->sw_dir_cor_sum ? nc : 0) : nullptr;
     a.sum_sw = d_sw.dev; a.sum_lit = d_lit.dev;
@@ -2448,6 +2481,7 @@ int hz_horizon_terrain_sw_dir_cor_coarse(hz_horizon_terrain *terrain, const floa
     a.surf_enl_fac = (const float *)t->enl; a.mask = (const uint8_t *)t->mask;
     a.cells = nc; a.azim_num = t->azim_num;
     a.fill = t->fill; a.dot_prod_min = cosf(deg2rad_f(t->ang_max));            // shadow_comp.cpp:498
+    a.refrac_fac = t->refrac_fac;
     a.weights = nullptr; a.acc_sw = a.acc_lit = nullptr; a.sum_sw = a.sum_lit = nullptr;
     a.first = a.last = 1;
     a.out_u8 = static_cast<uint8_t *>(codes.p);

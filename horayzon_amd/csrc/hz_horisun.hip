@@ -9,6 +9,7 @@
 // from its neighbour's, so those two loads are uncoalesced; the per-position outputs out[s][cell] are coalesced.
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
+#include "hz_horisun_refrac.h"
 
 namespace hz {
 
@@ -41,6 +42,8 @@ __device__ __forceinline__ bool horisun_shaded(const float *__restrict__ row, in
     return alpha < h;                                   // NaN horizon: false, the cell counts as lit
 }
 
+// REFRAC: the sun direction is bent by the atmospheric refraction first (clause 13; p.refrac_fac is not null)
+template <bool REFRAC>
 __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun(HorisunArgs p) {
     const size_t c = (size_t)blockIdx.x * HZ_HORISUN_TPB + threadIdx.x;
     if (c >= p.cells) return;
@@ -73,10 +76,13 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun(HorisunArgs p) {
     const float *row = p.hori + c * (size_t)p.azim_num;
     double a_sw = (p.sum_sw && !p.first) ? p.acc_sw[c] : 0.0;
     double a_lit = (p.sum_lit && !p.first) ? p.acc_lit[c] : 0.0;
+    double fac = 0.0;
+    if (REFRAC) fac = p.refrac_fac[c];
     for (int s = 0; s < p.num_sun; s++) {
         float sun_x = p.suns[3 * s] - ox, sun_y = p.suns[3 * s + 1] - oy, sun_z = p.suns[3 * s + 2] - oz;   // :422-425
         horisun_unit(sun_x, sun_y, sun_z);
-        const float dot_prod_ns = (norm_x * sun_x + norm_y * sun_y) + norm_z * sun_z;
+        float dot_prod_ns = (norm_x * sun_x + norm_y * sun_y) + norm_z * sun_z;
+        if (REFRAC) horisun_refract(fac, tilt_x, tilt_y, tilt_z, norm_x, norm_y, norm_z, sun_x, sun_y, sun_z, dot_prod_ns);
         const float dot_prod_ts = (tilt_x * sun_x + tilt_y * sun_y) + tilt_z * sun_z;
         int code = 1;                                   // self-shaded (shadow: !(dot_ts > 0))
         float val = 0.0f;                               // sw_dir_cor: 0 outside ang_max (!(dot_ts > dot_prod_min)) and in shadow
@@ -109,7 +115,8 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun(HorisunArgs p) {
 
 int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st) {
     if (a.cells == 0 || a.num_sun <= 0 || blocks == 0) return HZ_OK;
-    hipLaunchKernelGGL(k_horisun, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, a);
+    if (a.refrac_fac) hipLaunchKernelGGL(k_horisun<true>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, a);
+    else hipLaunchKernelGGL(k_horisun<false>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, a);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }

@@ -21,6 +21,7 @@
 // move); the library is built with -ffp-contract=off, so the values are the same words.
 #include "hz_internal.h"
 #include "hz_horisun_coarse_plan.h"
+#include "hz_horisun_refrac.h"
 
 namespace hz {
 
@@ -44,6 +45,7 @@ struct HorisunCoarseArgs {
     int nb, nstrips, rows, pitch, q;
     unsigned off_flags;                  // byte offset of the lit flags in dynamic LDS (the values are at 0)
     float *f_cor, *lit;                  // [num_sun][gy][gx] at the chunk's first position, or null
+    const double *refrac_fac;            // REFRAC: f64[cells], shadow_refrac_factor() (clause 13)
 };
 
 // one cell's frame
@@ -97,14 +99,16 @@ __device__ __forceinline__ void coarse_frame_load(const HorisunCoarseArgs &p, si
 }
 
 // clause 10 for one unmasked cell and one position: sw_dir_cor, and whether the cell is lit (shadow code 0)
-template <bool PLANES, bool CODES>
+template <bool PLANES, bool CODES, bool REFRAC>
 __device__ __forceinline__ void coarse_eval(const HorisunCoarseArgs &p, size_t cell, const float *__restrict__ sun, double per_rad,
                                             float &val, int &lit) {
     CoarseFrame f;
     coarse_frame_load(p, cell, f);
     float sun_x = sun[0] - f.ox, sun_y = sun[1] - f.oy, sun_z = sun[2] - f.oz;   // :422-425
     coarse_unit(sun_x, sun_y, sun_z);
-    const float dot_prod_ns = (f.norm_x * sun_x + f.norm_y * sun_y) + f.norm_z * sun_z;
+    float dot_prod_ns = (f.norm_x * sun_x + f.norm_y * sun_y) + f.norm_z * sun_z;
+    if (REFRAC)
+        horisun_refract(p.refrac_fac[cell], f.tilt_x, f.tilt_y, f.tilt_z, f.norm_x, f.norm_y, f.norm_z, sun_x, sun_y, sun_z, dot_prod_ns);
     const float dot_prod_ts = (f.tilt_x * sun_x + f.tilt_y * sun_y) + f.tilt_z * sun_z;
     // the look-up decides the code of every cell with dot_ts > 0, and the value of those with dot_ts > dot_prod_min (> 0)
     if (dot_prod_ts > (CODES ? 0.0f : p.dot_prod_min)) {
@@ -118,7 +122,7 @@ __device__ __forceinline__ void coarse_eval(const HorisunCoarseArgs &p, size_t c
     }
 }
 
-template <bool PLANES, bool CODES, bool VALS>
+template <bool PLANES, bool CODES, bool VALS, bool REFRAC>
 __global__ __launch_bounds__(HZ_HSC_TPB) void k_horisun_coarse(HorisunCoarseArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_hsc[];
     float *const lv = reinterpret_cast<float *>(smem_hsc);
@@ -146,7 +150,7 @@ __global__ __launch_bounds__(HZ_HSC_TPB) void k_horisun_coarse(HorisunCoarseArgs
             const size_t cell = cell00 + (size_t)r * (size_t)p.dim_1 + (size_t)c;
             float val = 0.0f;                           // sw_dir_cor: 0 outside ang_max (!(dot_ts > dot_prod_min)) and in shadow
             int lit = 0;
-            if (p.mask[cell] == 1) coarse_eval<PLANES, CODES>(p, cell, suns + 3 * q, per_rad, val, lit);
+            if (p.mask[cell] == 1) coarse_eval<PLANES, CODES, REFRAC>(p, cell, suns + 3 * q, per_rad, val, lit);
             const int at = q * p.pitch + r * Wm + c;
             if (VALS) lv[at] = val;
             if (CODES) lf[at] = (uint8_t)lit;
@@ -195,12 +199,13 @@ int horisun_coarse_launch(const HorisunArgs &a, bool planes, size_t plane_stride
     p.dim_1 = dim_1; p.p0 = p0; p.p1 = p1; p.gy = plan.gy; p.gx = plan.gx;
     p.nb = plan.nb; p.nstrips = plan.nstrips; p.rows = plan.rows; p.pitch = plan.pitch; p.q = plan.q;
     p.off_flags = plan.off_flags;
-    p.f_cor = f_cor; p.lit = lit;
+    p.f_cor = f_cor; p.lit = lit; p.refrac_fac = a.refrac_fac;
     const dim3 grid(plan.grid_x, horisun_coarse_groups(plan, a.num_sun));
     const size_t lds = plan.lds_bytes;
 #define HZ_LAUNCH_HSC(PL, C, V)                                                                                         \
     do {                                                                                                                \
-        hipLaunchKernelGGL((k_horisun_coarse<PL, C, V>), grid, dim3(HZ_HSC_TPB), lds, st, p);                           \
+        if (p.refrac_fac) hipLaunchKernelGGL((k_horisun_coarse<PL, C, V, true>), grid, dim3(HZ_HSC_TPB), lds, st, p);   \
+        else hipLaunchKernelGGL((k_horisun_coarse<PL, C, V, false>), grid, dim3(HZ_HSC_TPB), lds, st, p);               \
     } while (0)
 #define HZ_LAUNCH_HSC_OUT(PL)                                                                                           \
     do {                                                                                                                \

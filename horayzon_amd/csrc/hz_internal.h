@@ -266,6 +266,7 @@ struct HorisunArgs {
     double *acc_sw, *acc_lit;
     float *sum_sw, *sum_lit;
     int first, last;
+    const double *refrac_fac;            // null: no refraction; else f64[cells], shadow_refrac_factor() (clause 13)
 };
 int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st);
 

@@ -15,6 +15,7 @@
 // (that file's text does not move); both files are built with -ffp-contract=off, so the results are the same words.
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
+#include "hz_horisun_refrac.h"
 
 namespace hz {
 
@@ -140,6 +141,8 @@ __device__ __forceinline__ bool planes_shaded(const float *__restrict__ col, siz
     return alpha < h;                                   // NaN horizon: false, the cell counts as lit
 }
 
+// REFRAC: as k_horisun's
+template <bool REFRAC>
 __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun_planes(HorisunPlanesArgs q) {
     const HorisunArgs &p = q.a;
     const size_t c = (size_t)blockIdx.x * HZ_HORISUN_TPB + threadIdx.x;
@@ -173,10 +176,13 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun_planes(HorisunPlanes
     const float *col = p.hori + c;
     double a_sw = (p.sum_sw && !p.first) ? p.acc_sw[c] : 0.0;
     double a_lit = (p.sum_lit && !p.first) ? p.acc_lit[c] : 0.0;
+    double fac = 0.0;
+    if (REFRAC) fac = p.refrac_fac[c];
     for (int s = 0; s < p.num_sun; s++) {
         float sun_x = p.suns[3 * s] - ox, sun_y = p.suns[3 * s + 1] - oy, sun_z = p.suns[3 * s + 2] - oz;   // :422-425
         planes_unit(sun_x, sun_y, sun_z);
-        const float dot_prod_ns = (norm_x * sun_x + norm_y * sun_y) + norm_z * sun_z;
+        float dot_prod_ns = (norm_x * sun_x + norm_y * sun_y) + norm_z * sun_z;
+        if (REFRAC) horisun_refract(fac, tilt_x, tilt_y, tilt_z, norm_x, norm_y, norm_z, sun_x, sun_y, sun_z, dot_prod_ns);
         const float dot_prod_ts = (tilt_x * sun_x + tilt_y * sun_y) + tilt_z * sun_z;
         int code = 1;                                   // self-shaded (shadow: !(dot_ts > 0))
         float val = 0.0f;                               // sw_dir_cor: 0 outside ang_max (!(dot_ts > dot_prod_min)) and in shadow
@@ -211,7 +217,8 @@ int horisun_planes_launch(const HorisunArgs &a, size_t plane_stride, unsigned bl
     if (a.cells == 0 || a.num_sun <= 0 || blocks == 0) return HZ_OK;
     HorisunPlanesArgs q;
     q.a = a; q.stride = plane_stride;
-    hipLaunchKernelGGL(k_horisun_planes, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, q);
+    if (a.refrac_fac) hipLaunchKernelGGL(k_horisun_planes<true>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, q);
+    else hipLaunchKernelGGL(k_horisun_planes<false>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, q);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }

@@ -313,13 +313,15 @@ class HorizonTerrain:
     terrain-shaded when the sun's elevation in the cell's frame is below the horizon ``hori`` of ``horizon_gridded``,
     interpolated linearly at the sun's azimuth (clause 10).  No scene and no BVH; the self-shading and
     ``ang_max`` tests, the shadow codes, the ``sw_dir_cor`` formula and the sums of ``accumulate`` are ``Terrain``'s, and so
-    are the method names and signatures.  Atmospheric refraction is not covered: there is no ``refrac_cor`` and no
-    ``elevation`` argument."""
+    are the method names and signatures.  Atmospheric refraction is switched on by ``refraction(elevation)`` after
+    ``initialise`` (a method of its own: ``initialise`` keeps its arguments); every method then answers for the refracted
+    sun, with ``Terrain``'s ``refrac_cor=True`` set-up word for word (clause 13)."""
 
     def __init__(self, *, device=0):
         self._h = C.c_void_p()
         self._shape = None
         self._hori = None
+        self._refrac = False
         self.device = device
         self.last_stats = None
         _lib.check(_lib.lib().hz_horizon_terrain_create(device, C.byref(self._h)))
@@ -354,7 +356,8 @@ class HorizonTerrain:
         them (``azim[k] = 2 pi k / azim_num`` is the only layout supported; azim_num >= 1), the DEM vertices and the
         per-cell arrays of ``Terrain.initialise`` plus ``vec_north``.  ``hori`` is a NumPy array (copied to the GPU) or a
         torch tensor on the object's GPU (borrowed: the object holds a reference, the data must not change while it is in
-        use); the other arrays are NumPy and are copied.  No atmospheric refraction (no ``refrac_cor`` / ``elevation``)."""
+        use); the other arrays are NumPy and are copied.  Atmospheric refraction is off afterwards; ``refraction(elevation)``
+        switches it on."""
         self._initialise(False, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
                          vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max)
 
@@ -365,7 +368,8 @@ class HorizonTerrain:
         ``horizon_gridded(layout="azim_major")`` returns or ``horizon.to_azim_major`` makes of a cell-major horizon (NumPy:
         copied; torch tensor on the object's GPU: borrowed).  Every other argument and every check is ``initialise``'s,
         and so is every result of the methods, bit for bit; a wave's look-up is two loads of consecutive words per position
-        instead of one line per lane.  (A method of its own: ``initialise`` keeps exactly ``Terrain``-style arguments.)"""
+        instead of one line per lane, with atmospheric refraction (``refraction``) or without.  (A method of its own:
+        ``initialise`` keeps exactly ``Terrain``-style arguments.)"""
         self._initialise(True, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
                          vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max)
 
@@ -406,6 +410,7 @@ class HorizonTerrain:
 
         st = hz_stats()
         self._shape = None
+        self._refrac = False                                 # the library drops the factor with the old arrays
         L = _lib.lib()
         _lib.check((L.hz_horizon_terrain_initialise_planes if planes else L.hz_horizon_terrain_initialise)(
             self._h, ptr(hori), num, ptr(vert_grid), dem_dim_0, dem_dim_1, offset_0, offset_1,
@@ -414,6 +419,33 @@ class HorizonTerrain:
         self._hori = hori if _is_tensor(hori) else None      # keep a borrowed horizon alive
         self._shape = (vec_tilt.shape[0], vec_tilt.shape[1])
         self.last_stats = st.as_dict()
+
+    def refraction(self, elevation):
+        """Switch atmospheric refraction on or off for every later call (clause 13).  ``elevation``
+        f32 (y, x) [m]: the orthometric elevation of the inner-domain cells, ``Terrain.initialise``'s ``elevation`` (a
+        C-contiguous NumPy array, copied; no range check, as there); ``None`` switches it off.  With it, ``shadow``,
+        ``sw_dir_cor``, the batch forms, ``accumulate`` and ``sw_dir_cor_coarse`` answer for the sun as the atmosphere bends
+        it over each cell -- ``Terrain``'s ``refrac_cor=True`` -- on both horizon layouts.  ``initialise`` and
+        ``initialise_azim_major`` switch it off again."""
+        if elevation is not None:
+            _typed(elevation, np.float32, 2, "elevation")
+        if self._shape is None:
+            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
+        if elevation is not None:
+            if tuple(elevation.shape) != self._shape:
+                raise ValueError("array 'elevation' has incorrect shape")
+            if not elevation.flags["C_CONTIGUOUS"]:
+                raise ValueError("array 'elevation' is not C-contiguous")
+        st = hz_stats()
+        self._refrac = False
+        _lib.check(_lib.lib().hz_horizon_terrain_refraction(self._h, ptr(elevation), C.byref(st)))
+        self._refrac = elevation is not None
+        self.last_stats = st.as_dict()
+
+    @property
+    def refrac_cor(self):
+        """Whether the methods answer for the refracted sun (``refraction``)."""
+        return bool(getattr(self, "_refrac", False))
 
     _batch_out = staticmethod(Terrain._batch_out)
     _accum_arg = Terrain._accum_arg

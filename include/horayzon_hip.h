@@ -503,6 +503,17 @@ int hz_horizon_terrain_initialise_planes(hz_horizon_terrain* t, const float* pla
         const float* vert_grid, int dem_dim_0, int dem_dim_1, int offset_0, int offset_1,
         const float* vec_tilt, const float* vec_norm, const float* vec_north, int dim_in_0, int dim_in_1,
         const float* surf_enl_fac, const uint8_t* mask, float sw_dir_cor_fill, float ang_max, hz_stats* stats);
+/* Atmospheric refraction (DESIGN.md section 4 clause 13) on or off for every later call on the handle, both      */
+/* layouts, hz_horizon_terrain_run and both routes of hz_horizon_terrain_sw_dir_cor_coarse.  elevation           */
+/* f32[dim_in_0][dim_in_1] [m], host or device, copied: the orthometric elevation of the inner-domain cells,     */
+/* hz_terrain_initialise's; NULL = off.  On: the float32 set-up above becomes hz_terrain's with refrac_cor = 1,  */
+/* word for word -- elev_ang_true from the unrefracted dot_ns, Saemundsson's correction with the cell's          */
+/* pressure / temperature factor (float64, 8 B per cell, kept until destroy, initialise or NULL), s turned about */
+/* unit(s x norm) by it, dot_ns and dot_ts formed from the turned s', which also feeds the float64 look-up.  A   */
+/* sun at the cell's zenith gives NaN dot products: self-shaded.  hz_horizon_terrain_initialise(_planes)         */
+/* switches it off.  stats (may be NULL): t_h2d_s, t_total_s, num_cells.                                         */
+int hz_horizon_terrain_refraction(hz_horizon_terrain* t, const float* elevation /* f32[dim_in_0*dim_in_1]; NULL = off */,
+        hz_stats* stats /* may be NULL */);
 /* Any subset of the four outputs (at least one; NULL = not wanted; host or device pointers, all different) from  */
 /* one pass: positions go in chunks, one launch per chunk.  weights f32[num_sun], NULL = ones (the sums only).   */
 /* stats (may be NULL): t_kernel_s, t_d2h_s, t_total_s, num_cells, scratch_bytes = device memory of the call      */
@@ -516,7 +527,7 @@ int hz_horizon_terrain_run(hz_horizon_terrain* t, const float* sun_positions, co
 /*     sw_dir_cor for that cell and position (a masked or unlit cell may contribute +0.0 instead of being skipped: the           */
 /*     accumulator is never -0.0, so the add changes no bit);                                                                   */
 /*   sunlit_frac[s][I][J] = (float)((double)n_lit / (double)n), n_lit = the cells of B whose shadow code is 0;                   */
-/*   n == 0: both are sw_dir_cor_fill.  No atmospheric refraction.                                                              */
+/*   n == 0: both are sw_dir_cor_fill.  With hz_horizon_terrain_refraction on, v and the codes are the refracted sun's.          */
 /* pixel_per_gc_0 / _1 >= 1 and divisors of dim_in_0 / dim_in_1; f_cor, sunlit_frac f32[num_sun][gy][gx], NULL = not wanted (at */
 /* least one; they must differ); positions and outputs host or device pointers.  The look-up is evaluated for the cells with    */
 /* dot_ts > 0 if sunlit_frac is wanted (it serves both outputs), else for dot_ts > dot_prod_min.  Both horizon layouts give the */

@@ -2,14 +2,15 @@
 synth.sun_positions, 43 x 43 blocks), everything resident in HBM: the fused kernel against the two-pass route (the parent
 commit's kernels) in the same process, for both horizon layouts.
 
-    python scripts/horisun_coarse_perf.py [--tile N] [--suns S] [--pixels P] [--passes K] [--out FILE]
+    python scripts/horisun_coarse_perf.py [--tile N] [--suns S] [--pixels P] [--passes K] [--refrac] [--out FILE]
 
 The tile's own horizon (guess_constant, dist_search 50 km, hori_acc 0.25 deg) is computed once into HBM, and
 horizon.to_azim_major of it.  One warm-up, then the median of --passes timed passes of each call; one JSON line per row, with
 the spread (max - min) of the passes.  Rows, per layout: fused with both outputs, fused with f_cor only, the two-pass route
 (both outputs), and sw_dir_cor_batch + shadow_batch into HBM (the same information as maps, without the reduction); and
 Terrain.sw_dir_cor_coarse (ray casting) on the same tile for context.  Untimed, word for word on the whole tile: fused
-against two-pass, and planes against cell-major."""
+against two-pass, and planes against cell-major.  --refrac: every row and every comparison again, marked "refrac": true, with
+refraction(elevation) on (DESIGN.md section 4 clause 13), and Terrain(refrac_cor=True).sw_dir_cor_coarse for context."""
 import argparse
 import ctypes as C
 import json
@@ -43,6 +44,7 @@ def main():
     ap.add_argument("--pixels", type=int, default=43)
     ap.add_argument("--dist-search", type=float, default=50.0)
     ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--refrac", action="store_true", help="the rows again with atmospheric refraction on")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "horisun_coarse", "horisun_coarse_perf.jsonl"))
     args = ap.parse_args()
     import torch
@@ -121,36 +123,43 @@ def main():
         emit(d)
         return wall, spread
 
-    walls = {}
-    for layout, t in objs.items():
-        f0, l0, f1, f2, l2 = table(), table(), table(), table(), table()
-        tables[layout] = (f0, l0, f1, f2, l2)
-        knob(b"horisun_coarse_route", 0)
-        walls[(layout, "fused")] = row("fused", layout, t, lambda: t.sw_dir_cor_coarse(d_suns, P, f_cor=f0, sunlit_frac=l0))
-        row("fused_f_cor_only", layout, t, lambda: t.sw_dir_cor_coarse(d_suns, P, f_cor=f1))
-        knob(b"horisun_coarse_route", 1)
-        walls[(layout, "two_pass")] = row("two_pass", layout, t, lambda: t.sw_dir_cor_coarse(d_suns, P, f_cor=f2, sunlit_frac=l2))
-        knob(b"horisun_coarse_route", -1)
+    def measure(tag):
+        walls = {}
+        for layout, t in objs.items():
+            f0, l0, f1, f2, l2 = table(), table(), table(), table(), table()
+            tables[layout] = (f0, l0, f1, f2, l2)
+            knob(b"horisun_coarse_route", 0)
+            walls[(layout, "fused")] = row("fused", layout, t, lambda: t.sw_dir_cor_coarse(d_suns, P, f_cor=f0, sunlit_frac=l0), tag)
+            row("fused_f_cor_only", layout, t, lambda: t.sw_dir_cor_coarse(d_suns, P, f_cor=f1), tag)
+            knob(b"horisun_coarse_route", 1)
+            walls[(layout, "two_pass")] = row("two_pass", layout, t, lambda: t.sw_dir_cor_coarse(d_suns, P, f_cor=f2, sunlit_frac=l2), tag)
+            knob(b"horisun_coarse_route", -1)
 
-        def maps():
-            t.sw_dir_cor_batch(suns, d_sw)
-            k = t.last_stats["t_kernel_s"]
-            t.shadow_batch(suns, d_sh)
-            t.last_stats["t_kernel_s"] += k
-        row("batch_maps_into_hbm", layout, t, maps, {"map_bytes": int(d_sw.numel()) * 4 + int(d_sh.numel())})
+            def maps():
+                t.sw_dir_cor_batch(suns, d_sw)
+                k = t.last_stats["t_kernel_s"]
+                t.shadow_batch(suns, d_sh)
+                t.last_stats["t_kernel_s"] += k
+            row("batch_maps_into_hbm", layout, t, maps, {"map_bytes": int(d_sw.numel()) * 4 + int(d_sh.numel()), **tag})
 
-    def words(a, b):
-        return bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
-    for layout in objs:
-        f0, l0, f1, f2, l2 = tables[layout]
-        emit({"figure": "equal", "what": "fused against two_pass", "layout": layout,
-              "f_cor": words(f0, f2), "sunlit_frac": words(l0, l2), "f_cor_only": words(f1, f0)})
-    a, b = tables["cell_major"], tables["azim_major"]
-    emit({"figure": "equal", "what": "azim_major against cell_major", "f_cor": words(a[0], b[0]), "sunlit_frac": words(a[1], b[1])})
-    for layout in objs:
-        (wf, sf), (wt, s2) = walls[(layout, "fused")], walls[(layout, "two_pass")]
-        emit({"figure": "verdict", "layout": layout, "fused_wall_ms": round(1e3 * wf, 2), "two_pass_wall_ms": round(1e3 * wt, 2),
-              "margin_ms": round(1e3 * max(sf, s2), 2), "fused_is_not_slower": bool(wf <= wt + max(sf, s2))})
+        def words(a, b):
+            return bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
+        for layout in objs:
+            f0, l0, f1, f2, l2 = tables[layout]
+            emit({"figure": "equal", "what": "fused against two_pass", "layout": layout, **tag,
+                  "f_cor": words(f0, f2), "sunlit_frac": words(l0, l2), "f_cor_only": words(f1, f0)})
+        a, b = tables["cell_major"], tables["azim_major"]
+        emit({"figure": "equal", "what": "azim_major against cell_major", **tag, "f_cor": words(a[0], b[0]), "sunlit_frac": words(a[1], b[1])})
+        for layout in objs:
+            (wf, sf), (wt, s2) = walls[(layout, "fused")], walls[(layout, "two_pass")]
+            emit({"figure": "verdict", "layout": layout, **tag, "fused_wall_ms": round(1e3 * wf, 2), "two_pass_wall_ms": round(1e3 * wt, 2),
+                  "margin_ms": round(1e3 * max(sf, s2), 2), "fused_is_not_slower": bool(wf <= wt + max(sf, s2))})
+
+    measure({})
+    if args.refrac:
+        for t in objs.values():
+            t.refraction(elev)
+        measure({"refrac": True})
 
     # context: ray casting, the same tile and blocks
     del d_sw, d_sh
@@ -158,6 +167,11 @@ def main():
     tr.initialise(g["vert_grid"], n, n, off, off, vec_tilt, vec_norm, enl, elev, mask, sw_dir_cor_fill=-7.0, scene=scene)
     fr, lr = table(), table()
     row("Terrain.sw_dir_cor_coarse", None, tr, lambda: tr.sw_dir_cor_coarse(d_suns, P, f_cor=fr, sunlit_frac=lr))
+    if args.refrac:
+        tr.initialise(g["vert_grid"], n, n, off, off, vec_tilt, vec_norm, enl, elev, mask, sw_dir_cor_fill=-7.0, refrac_cor=True,
+                      scene=scene)
+        row("Terrain.sw_dir_cor_coarse", None, tr, lambda: tr.sw_dir_cor_coarse(d_suns, P, f_cor=fr, sunlit_frac=lr),
+            {"refrac": True})
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

@@ -1,7 +1,7 @@
 """HorizonTerrain on the c3 tile (3601^2, 360 azimuths, the 144 sun positions of synth.sun_positions), everything resident in
 HBM, against Terrain's ray casting of the same commit on the same box in the same run.
 
-    python scripts/horisun_perf.py [--tile N] [--suns S] [--window W] [--layout both|cell_major|azim_major] [--out FILE]
+    python scripts/horisun_perf.py [--tile N] [--suns S] [--window W] [--layout both|cell_major|azim_major] [--refrac] [--out FILE]
     python scripts/horisun_perf.py --pmc [--layout cell_major|azim_major]   # only HorizonTerrain.sw_dir_cor_batch of one layout
         (k_horisun or k_horisun_planes), for a counter run of its own:
         rocprofv3 --pmc FETCH_SIZE --output-format csv -d <dir> -- python scripts/horisun_perf.py --pmc --layout azim_major
@@ -18,7 +18,11 @@ borrowed by HorizonTerrain.  One warm-up and one timed pass of each call; one JS
   (d) the azimuth-major layout (--layout both, the default; DESIGN.md section 4 clause 11), in the same run: the wall time of the
       horizon call into planes in HBM against the cell-major call, of to_azim_major on the tile's horizon, and (a) for a
       HorizonTerrain that reads the planes; the planes of the horizon call and of to_azim_major, and every output of the two
-      layouts, are compared word for word on the whole tile.
+      layouts, are compared word for word on the whole tile;
+  (e) --refrac: atmospheric refraction (DESIGN.md section 4 clause 13), in the same run: the rows of (a) again, marked
+      "refrac": true, for HorizonTerrain with refraction(elevation) on in the layouts of the run and for Terrain(refrac_cor=True)
+      as context, the outputs of the two layouts compared word for word on the whole tile, and the agreement of (c) for the
+      refracted sun.
 """
 import argparse
 import ctypes as C
@@ -88,6 +92,7 @@ def main():
     ap.add_argument("--dist-search", type=float, default=50.0)
     ap.add_argument("--pmc", action="store_true")
     ap.add_argument("--layout", choices=("both", "cell_major", "azim_major"), default="both")
+    ap.add_argument("--refrac", action="store_true", help="the speed rows again with atmospheric refraction on")
     ap.add_argument("--passes", type=int, default=3, help="timed passes of the layout figures (after one warm-up)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -191,35 +196,45 @@ def main():
         d_sw_p = torch.empty((S,) + shape, dtype=torch.float32, device=dev)
         d_sum_p, d_lit_p = torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev)
     classes.append(("Terrain", None, tr))
-    for call in ("sw_dir_cor_batch", "shadow_batch", "accumulate"):
-        for name, layout, t in classes:
-            p = layout == "azim_major"
-            if call == "sw_dir_cor_batch":
-                fn = lambda: t.sw_dir_cor_batch(suns, d_sw_p if p else d_sw)
-            elif call == "shadow_batch":
-                fn = lambda: t.shadow_batch(suns, d_sh["azim_major" if p else name])
-            else:
-                fn = lambda: t.accumulate(d_suns, None, sw_dir_cor_sum=d_sum_p if p else d_sum, sunlit_sum=d_lit_p if p else d_lit)
-            _, wall = timed(fn, args.passes if layout else 1)
+
+    def speed(classes, refrac):
+        for call in ("sw_dir_cor_batch", "shadow_batch", "accumulate"):
+            for name, layout, t in classes:
+                p = layout == "azim_major"
+                if call == "sw_dir_cor_batch":
+                    fn = lambda: t.sw_dir_cor_batch(suns, d_sw_p if p else d_sw)
+                elif call == "shadow_batch":
+                    fn = lambda: t.shadow_batch(suns, d_sh["azim_major" if p else name])
+                else:
+                    fn = lambda: t.accumulate(d_suns, None, sw_dir_cor_sum=d_sum_p if p else d_sum, sunlit_sum=d_lit_p if p else d_lit)
+                _, wall = timed(fn, args.passes if layout else 1)
+                torch.cuda.synchronize()
+                d = {"figure": "speed", "class": name, "call": call, "tile": n, "suns": S,
+                     "kernel_ms_per_position": round(1e3 * t.last_stats["t_kernel_s"] / S, 4),
+                     "wall_ms_per_position": round(1e3 * wall / S, 4), "scratch_bytes": t.last_stats["scratch_bytes"]}
+                if layout:
+                    d["layout"] = layout
+                if refrac:
+                    d["refrac"] = True
+                emit(d)
+            if planes and args.layout == "both" and call != "accumulate":
+                if call == "sw_dir_cor_batch":
+                    # (Terrain's maps went to d_sw last: run the cell-major HorizonTerrain once more)
+                    th.sw_dir_cor_batch(suns, d_sw)
+                    torch.cuda.synchronize()
+                a, b = (d_sw_p, d_sw) if call == "sw_dir_cor_batch" else (d_sh["azim_major"], d_sh["HorizonTerrain"])
+                emit({"figure": "layouts_equal", "call": call, **({"refrac": True} if refrac else {}),
+                      "equal": bool(torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a,
+                                                b.view(torch.int32) if b.dtype == torch.float32 else b))})
+        if planes and args.layout == "both":
+            # (the sums of Terrain's accumulate went to d_sum / d_lit last: run the cell-major HorizonTerrain once more)
+            th.accumulate(d_suns, None, sw_dir_cor_sum=d_sum, sunlit_sum=d_lit)
             torch.cuda.synchronize()
-            d = {"figure": "speed", "class": name, "call": call, "tile": n, "suns": S,
-                 "kernel_ms_per_position": round(1e3 * t.last_stats["t_kernel_s"] / S, 4),
-                 "wall_ms_per_position": round(1e3 * wall / S, 4), "scratch_bytes": t.last_stats["scratch_bytes"]}
-            if layout:
-                d["layout"] = layout
-            emit(d)
-        if planes and args.layout == "both" and call != "accumulate":
-            a, b = (d_sw_p, d_sw) if call == "sw_dir_cor_batch" else (d_sh["azim_major"], d_sh["HorizonTerrain"])
-            emit({"figure": "layouts_equal", "call": call,
-                  "equal": bool(torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a,
-                                            b.view(torch.int32) if b.dtype == torch.float32 else b))})
-    if planes and args.layout == "both":
-        # (the sums of Terrain's accumulate went to d_sum / d_lit last: run the cell-major HorizonTerrain once more)
-        th.accumulate(d_suns, None, sw_dir_cor_sum=d_sum, sunlit_sum=d_lit)
-        torch.cuda.synchronize()
-        emit({"figure": "layouts_equal", "call": "accumulate",
-              "equal": bool(torch.equal(d_sum.view(torch.int32), d_sum_p.view(torch.int32))
-                            and torch.equal(d_lit.view(torch.int32), d_lit_p.view(torch.int32)))})
+            emit({"figure": "layouts_equal", "call": "accumulate", **({"refrac": True} if refrac else {}),
+                  "equal": bool(torch.equal(d_sum.view(torch.int32), d_sum_p.view(torch.int32))
+                                and torch.equal(d_lit.view(torch.int32), d_lit_p.view(torch.int32)))})
+
+    speed(classes, False)
 
     # (c) agreement of the look-up with ray casting on the tile's own horizon
     codes_h = d_sh["azim_major" if args.layout == "azim_major" else "HorizonTerrain"]
@@ -245,6 +260,19 @@ def main():
     emit({"figure": "horizon_lines", "window": W, "distinct_128B_lines_window": touched,
           "bytes_scaled_to_tile": int(touched * 128 * scale), "hori_bytes": int(d_hori.numel()) * 4,
           "output_bytes_sw_dir_cor_batch": S * in0 * in1 * 4})
+    # (e) the same rows with atmospheric refraction
+    if args.refrac:
+        tr_r = hz.shadow.Terrain()
+        tr_r.initialise(g["vert_grid"], n, n, off, off, vec_tilt, vec_norm, enl, elev, mask, sw_dir_cor_fill=-7.0,
+                        refrac_cor=True, scene=scene)
+        for _, _, t in classes[:-1]:
+            t.refraction(elev)
+        speed(classes[:-1] + [("Terrain", None, tr_r)], True)
+        same = 0
+        for s in range(S):
+            same += int((codes_h[s] == d_sh["Terrain"][s]).sum())
+        emit({"figure": "agreement_with_ray_casting", "refrac": True, "pairs": S * in0 * in1,
+              "share_equal": round(same / (S * in0 * in1), 6)})
     if args.out:
         with open(args.out, "w") as f:
             for d in lines:
