@@ -69,6 +69,15 @@ class hz_horisun_out(C.Structure):
         super().__init__(C.sizeof(hz_horisun_out), shadow, sw_dir_cor, sw_dir_cor_sum, sunlit_sum)
 
 
+class hz_suntimes_out(C.Structure):
+    """Outputs of hz_horizon_terrain_sun_times (None: not wanted); `size` is set to sizeof(hz_suntimes_out)."""
+    _fields_ = [("size", C.c_int32), ("sunrise", C.c_void_p), ("sunset", C.c_void_p),
+                ("duration", C.c_void_p), ("intervals", C.c_void_p)]
+
+    def __init__(self, sunrise=None, sunset=None, duration=None, intervals=None):
+        super().__init__(C.sizeof(hz_suntimes_out), sunrise, sunset, duration, intervals)
+
+
 # every symbol include/horayzon_hip.h declares (tests check that all are exported)
 SYMBOLS = (
     "hz_last_error", "hz_abi_struct_sizes", "hz_abi_version", "hz_device_count", "hz_device_info",
@@ -89,7 +98,7 @@ SYMBOLS = (
     "hz_horizon_terrain_create", "hz_horizon_terrain_initialise", "hz_horizon_terrain_run", "hz_horizon_terrain_destroy",
     "hz_horizon_gridded_planes", "hz_horizon_gridded_scene_planes", "hz_hori_to_planes", "hz_hori_from_planes",
     "hz_topo_params_planes", "hz_horizon_terrain_initialise_planes",
-    "hz_horizon_terrain_sw_dir_cor_coarse", "hz_horizon_terrain_refraction",
+    "hz_horizon_terrain_sw_dir_cor_coarse", "hz_horizon_terrain_refraction", "hz_horizon_terrain_sun_times",
 )
 
 
@@ -203,6 +212,7 @@ def lib():
     L.hz_horizon_terrain_run.argtypes = [vp, vp, vp, ip, C.POINTER(hz_horisun_out), C.POINTER(hz_stats)]
     L.hz_horizon_terrain_sw_dir_cor_coarse.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.POINTER(hz_stats)]
     L.hz_horizon_terrain_refraction.argtypes = [vp, vp, C.POINTER(hz_stats)]
+    L.hz_horizon_terrain_sun_times.argtypes = [vp, vp, vp, ip, C.POINTER(hz_suntimes_out), C.POINTER(hz_stats)]
     L.hz_horizon_terrain_destroy.argtypes = [vp]
     for name in SYMBOLS:
         if name not in ("hz_last_error", "hz_vert_grid_len"):

@@ -2528,6 +2528,113 @@ int hz_horizon_terrain_sw_dir_cor_coarse(hz_horizon_terrain *terrain, const floa
     return HZ_OK;
 }
 
+// HorizonTerrain.sun_times (DESIGN.md section 4 clause 14; k_suntimes, hz_suntimes.hip): the position chunks of
+// hz_horizon_terrain_run, each lane's running state in registers during a launch and in 44 B per cell between the launches of a
+// call.  times[s0 - 1] of a chunk travels as a kernel argument; host positions and times go up one chunk at a time.
+int hz_horizon_terrain_sun_times(hz_horizon_terrain *terrain, const float *sun_positions, const double *times, int num_sun,
+                                 const hz_suntimes_out *out, hz_stats *stats) {
+    HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "HorizonTerrain is not initialised");
+    if (!sun_positions || num_sun <= 0) return set_error(HZ_ERR_ARG, "array 'sun_positions' has incorrect shape");
+    if (!times) return set_error(HZ_ERR_ARG, "array 'times' has incorrect shape");
+    if (!out || out->size != (int32_t)sizeof(hz_suntimes_out))
+        return set_error(HZ_ERR_ARG, "hz_suntimes_out.size is %d, expected %d", out ? (int)out->size : 0, (int)sizeof(hz_suntimes_out));
+    const void *outs[4] = {out->sunrise, out->sunset, out->duration, out->intervals};
+    if (!outs[0] && !outs[1] && !outs[2] && !outs[3]) return set_error(HZ_ERR_ARG, "no output buffer (every pointer of hz_suntimes_out is NULL)");
+    for (int i = 0; i < 4; i++)
+        for (int j = i + 1; j < 4; j++)
+            if (outs[i] && outs[i] == outs[j]) return set_error(HZ_ERR_ARG, "the outputs must be different arrays");
+    HorisunPlan plan;
+    if (horisun_plan(t->dim_in_0, t->dim_in_1, t->azim_num, num_sun, g_horisun_chunk.load(std::memory_order_relaxed), 0, &plan))
+        return set_error(HZ_ERR_ARG, "too many sun positions");
+    std::lock_guard<std::mutex> run_lock(t->run_mu);
+    HZ_HIP(hipSetDevice(t->device));
+    hipStream_t st = t->stream;
+    Timer t_total; t_total.start();
+    const bool sun_on_dev = is_device_ptr(sun_positions), times_on_dev = is_device_ptr(times);
+    // the times on the host: they are checked here, and the one before each chunk is a kernel argument
+    std::vector<double> times_down;
+    const double *times_host = times;
+    if (times_on_dev) {
+        times_down.resize((size_t)num_sun);
+        HZ_HIP(hipMemcpy(times_down.data(), times, (size_t)num_sun * sizeof(double), hipMemcpyDeviceToHost));
+        times_host = times_down.data();
+    }
+    for (int s = 0; s < num_sun; s++)
+        if (!std::isfinite(times_host[s]) || (s > 0 && !(times_host[s] > times_host[s - 1])))
+            return set_error(HZ_ERR_ARG, "'times' must be finite and strictly increasing (times[%d])", s);
+    const size_t nc = plan.cells;
+    const int k = plan.chunk;
+    DevScratch state, stage;
+    size_t scratch = 0;
+    if (plan.num_chunks > 1) { HZ_HIP(hipMalloc(&state.p, suntimes_state_bytes(nc))); scratch += suntimes_state_bytes(nc); }
+    double *stage_times = nullptr; float *stage_sun = nullptr;   // host times / positions go up one chunk at a time
+    if (!sun_on_dev || !times_on_dev) {
+        HZ_HIP(hipMalloc(&stage.p, (size_t)k * (sizeof(double) + 3 * sizeof(float)))); scratch += (size_t)k * (sizeof(double) + 3 * sizeof(float));
+        stage_times = static_cast<double *>(stage.p); stage_sun = reinterpret_cast<float *>(stage_times + k);
+    }
+    DevOut<float> d_rise, d_set, d_dur; DevOut<int32_t> d_n;
+    int rc;
+    if ((rc = d_rise.bind(out->sunrise, out->sunrise ? nc : 0))) return rc;
+    if ((rc = d_set.bind(out->sunset, out->sunset ? nc : 0))) return rc;
+    if ((rc = d_dur.bind(out->duration, out->duration ? nc : 0))) return rc;
+    if ((rc = d_n.bind(out->intervals, out->intervals ? nc : 0))) return rc;
+    for (const void *owned : {d_rise.owned, d_set.owned, d_dur.owned, d_n.owned})
+        if (owned) scratch += nc * 4;
+    SuntimesArgs a;
+    a.hori = t->hori; a.stride = nc; a.vert = (const float *)t->vert;
+    a.vec_tilt = (const float *)t->tilt; a.vec_norm = (const float *)t->norm; a.vec_north = (const float *)t->north;
+    a.mask = (const uint8_t *)t->mask;
+    a.cells = nc; a.azim_num = t->azim_num;
+    a.fill = t->fill;
+    a.refrac_fac = t->refrac_fac;
+    a.state = static_cast<double *>(state.p);
+    a.state_n = state.p ? reinterpret_cast<int32_t *>(a.state + 5 * nc) : nullptr;
+    a.sunrise = d_rise.dev; a.sunset = d_set.dev; a.duration = d_dur.dev; a.intervals = d_n.dev;
+    float ms = 0.0f;
+    {
+        hipEvent_t e0, e1;
+        HZ_HIP(hipEventCreate(&e0)); HZ_HIP(hipEventCreate(&e1));
+        struct EvFree { hipEvent_t a, b; ~EvFree() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev_free{e0, e1};
+        HZ_HIP(hipEventRecord(e0, st));
+        for (int c = 0; c < plan.num_chunks; c++) {
+            int s0 = 0, kc = 0;
+            horisun_chunk(plan, num_sun, c, &s0, &kc);
+            if (sun_on_dev) a.suns = sun_positions + 3 * (size_t)s0;
+            else {
+                HZ_HIP(hipMemcpyAsync(stage_sun, sun_positions + 3 * (size_t)s0, (size_t)kc * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+                a.suns = stage_sun;
+            }
+            if (times_on_dev) a.times = times + s0;
+            else {
+                HZ_HIP(hipMemcpyAsync(stage_times, times + s0, (size_t)kc * sizeof(double), hipMemcpyHostToDevice, st));
+                a.times = stage_times;
+            }
+            a.t_before = s0 > 0 ? times_host[s0 - 1] : times_host[0];
+            a.num_sun = kc;
+            a.first = c == 0; a.last = c == plan.num_chunks - 1;
+            if ((rc = suntimes_launch(a, t->planes, plan.blocks, st))) return rc;
+        }
+        HZ_HIP(hipEventRecord(e1, st));
+        HZ_HIP(hipEventSynchronize(e1));
+        HZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+    }
+    Timer t_d2h; t_d2h.start();
+    if ((rc = d_rise.finish(st))) return rc;
+    if ((rc = d_set.finish(st))) return rc;
+    if ((rc = d_dur.finish(st))) return rc;
+    if ((rc = d_n.finish(st))) return rc;
+    HZ_HIP(hipStreamSynchronize(st));
+    if (stats) {
+        stats->num_cells = nc;
+        stats->t_kernel_s += (double)ms * 1e-3;
+        stats->t_d2h_s += t_d2h.stop();
+        stats->t_total_s += t_total.stop();
+        stats->scratch_bytes = scratch;
+    }
+    return HZ_OK;
+}
+
 int hz_horizon_terrain_destroy(hz_horizon_terrain *terrain) {
     HorizonTerrain *t = reinterpret_cast<HorizonTerrain *>(terrain);
     if (!t) return HZ_OK;

@@ -292,6 +292,33 @@ int horisun_coarse_plan_for(int dim_0, int dim_1, int p0, int p1, int chunk, boo
 int horisun_coarse_launch(const HorisunArgs &a, bool planes, size_t plane_stride, const HorisunCoarsePlan &plan,
                           const unsigned *n, int dim_1, int p0, int p1, float *f_cor, float *lit, hipStream_t st);
 
+// hz_suntimes.hip (hz_horizon_terrain_sun_times; device pointers; DESIGN.md section 4, clause 14): one launch of k_suntimes over
+// num_sun positions of a sun track, one lane per cell.  times f64[num_sun] = the times of those positions, t_before = the time of
+// the position before the launch's first (not read in the first launch).  The per-cell state starts empty (first) or comes
+// from state f64[5][cells] (rise, set, dur, open, g_prev) and state_n i32[cells] (2 * n + lit_prev), and goes back there or,
+// in the last launch of a call, to the maps sunrise / sunset / duration f32[cells] and intervals i32[cells] (null: not wanted;
+// masked cells: fill, -1).  A call of one launch (first and last) needs no state.  planes: hori = f32[azim_num][stride]
+struct SuntimesArgs {
+    const float *hori;                   // f32[cells][azim_num], or planes
+    size_t stride;                       // planes: words from one azimuth's plane to the next
+    const float *vert;                   // f32[cells][3]: the vertices of the inner domain
+    const float *vec_tilt, *vec_norm, *vec_north;
+    const uint8_t *mask;
+    size_t cells;
+    int azim_num;
+    const float *suns;                   // f32[num_sun][3]
+    const double *times;                 // f64[num_sun]
+    double t_before;
+    int num_sun;
+    float fill;
+    int first, last;
+    const double *refrac_fac;            // null: no refraction; else f64[cells] (clause 13)
+    double *state; int32_t *state_n;
+    float *sunrise, *sunset, *duration; int32_t *intervals;
+};
+size_t suntimes_state_bytes(size_t cells);
+int suntimes_launch(const SuntimesArgs &a, bool planes, unsigned blocks, hipStream_t st);
+
 // hz_sort.hip: hand-written stable LSD radix sort (pairs) and exclusive scan, uint32
 size_t sort_temp_elems(size_t n);
 size_t scan_temp_elems(size_t n);

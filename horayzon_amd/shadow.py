@@ -595,3 +595,66 @@ class HorizonTerrain:
         _lib.check(_lib.lib().hz_horizon_terrain_sw_dir_cor_coarse(
             self._h, ptr(sun_positions), sun_positions.shape[0], p0, p1, ptr(f_cor), ptr(sunlit_frac), C.byref(st)))
         self.last_stats = st.as_dict()
+
+    def _sun_times_out(self, buf, np_dtype, name):
+        """Output map of ``sun_times``: a NumPy array, or a torch tensor on the object's GPU."""
+        if isinstance(buf, np.ndarray):
+            _typed(buf, np_dtype, 2, name)
+            return
+        if not hasattr(buf, "data_ptr"):
+            raise TypeError("Argument '%s' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
+                            % (name, type(buf).__name__))
+        if buf.dim() != 2:
+            raise ValueError("Buffer has wrong number of dimensions (expected 2, got %d)" % buf.dim())
+        if str(buf.dtype).split(".")[-1] != np.dtype(np_dtype).name:
+            raise ValueError("Buffer dtype mismatch, expected '%s' but got '%s'" % (np.dtype(np_dtype).name, buf.dtype))
+        if buf.device.type != "cuda" or buf.device.index != self.device:
+            raise ValueError("tensor '%s' is not on the HorizonTerrain's device (cuda:%d)" % (name, self.device))
+
+    def sun_times(self, sun_positions, times, *, sunrise=None, sunset=None, duration=None, intervals=None):
+        """Maps over a sun track (clause 14): sun_positions f32[S][3] (S >= 1) at the ``times``
+        f64[S] (a NumPy array: finite, strictly increasing, in the caller's unit).  Per cell: ``sunrise`` = the time the sun
+        first clears terrain and surface, ``sunset`` = the time it last does, ``duration`` = the sunlit time in between,
+        ``intervals`` = the number of separate sunlit spells (a peak that interrupts the sun gives two).  A position is sunlit
+        exactly where ``shadow()`` gives 0.  Between two positions with different states the crossing time is interpolated
+        linearly from the sun's clearances g = min(alpha - h, asin(dot_ts)) [rad] at the two, so a coarse track gives event
+        times far finer than its step; a cell lit at the first or last position gets ``times[0]`` / ``times[-1]``.  Cells
+        never lit get NaN, NaN, 0.0 and 0; masked cells ``sw_dir_cor_fill`` and -1.  Outputs f32[y][x] (``intervals``:
+        i32[y][x]), NumPy or torch tensors on the object's GPU; any subset, at least one.  Works with ``refraction`` on and in
+        both horizon layouts (the same words).  Device memory besides the buffers is 44 B per cell when the track spans
+        several launches and does not grow with S (``last_stats["scratch_bytes"]``).  ``Terrain`` (the ray path) has no such
+        method: a ray says whether the sun is hidden, not by how much it clears, so there is nothing to interpolate."""
+        outs = (("sunrise", sunrise, np.float32), ("sunset", sunset, np.float32), ("duration", duration, np.float32),
+                ("intervals", intervals, np.int32))
+        self._accum_arg(sun_positions, 2, "sun_positions")
+        _typed(times, np.float64, 1, "times")
+        for name, buf, dtype in outs:
+            if buf is not None:
+                self._sun_times_out(buf, dtype, name)
+        if self._shape is None:
+            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
+        given = [(name, buf) for name, buf, _ in outs if buf is not None]
+
+        def contiguous(a):
+            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
+        V.run((
+            (ValueError, "at least one of 'sunrise', 'sunset', 'duration' and 'intervals' must be given", lambda: not given),
+            (ValueError, "array 'sun_positions' has incorrect shape",
+             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
+            (ValueError, "array 'times' has incorrect shape", lambda: times.shape[0] != sun_positions.shape[0]),
+        ) + tuple(
+            (ValueError, "array '%s' has incorrect shape" % name, lambda buf=buf: tuple(buf.shape) != self._shape)
+            for name, buf in given
+        ) + (
+            (ValueError, "not all input arrays are C-contiguous",
+             lambda: not all(contiguous(a) for a in [sun_positions, times] + [buf for _, buf in given])),
+            (ValueError, "'sunrise', 'sunset', 'duration' and 'intervals' must be different arrays",
+             lambda: len({ptr(buf) for _, buf in given}) != len(given)),
+            (ValueError, "'times' must be finite and strictly increasing",
+             lambda: not (np.isfinite(times).all() and (np.diff(times) > 0.0).all())),
+        ))
+        st = hz_stats()
+        out = _lib.hz_suntimes_out(**{name: ptr(buf) for name, buf in given})
+        _lib.check(_lib.lib().hz_horizon_terrain_sun_times(self._h, ptr(sun_positions), ptr(times), sun_positions.shape[0],
+                                                           C.byref(out), C.byref(st)))
+        self.last_stats = st.as_dict()

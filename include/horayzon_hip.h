@@ -520,6 +520,35 @@ int hz_horizon_terrain_refraction(hz_horizon_terrain* t, const float* elevation 
 /* besides per-position maps staged for host outputs; it does not grow with num_sun                             */
 int hz_horizon_terrain_run(hz_horizon_terrain* t, const float* sun_positions, const float* weights /* NULL = ones */,
         int num_sun, const hz_horisun_out* out, hz_stats* stats);
+/* DESIGN.md section 4 clause 14: sunrise, sunset, sunshine duration and the number of sunlit spells per cell over a sun track.  */
+/* sun_positions f32[num_sun][3], times f64[num_sun] (finite, strictly increasing, the caller's unit), num_sun >= 1.  For every   */
+/* unmasked cell, in ascending s:                                                                                                 */
+/*   set-up: the float32 set-up above (with hz_horizon_terrain_refraction on: the refracted one, steps 1 - 7 of clause 13 for     */
+/*     every cell, without the early exit for back slopes) gives s, dot_ns, dot_ts;                                               */
+/*   look-up, for EVERY position, also where dot_ts <= 0: h and alpha as above; d = alpha - h (float64; NaN for a NaN horizon),   */
+/*     beta = asin(fmin(fmax((double)dot_ts, -1.0), 1.0)), g = fmin(d, beta) (IEEE fmin: a NaN d leaves beta) -- the sun's          */
+/*     clearance over terrain and surface [rad];                                                                                  */
+/*   lit = dot_ts > 0 && !(alpha < h): exactly "shadow gives 0" for that cell and position; g never decides it;                    */
+/*   events: s = 0: if lit, open = rise = times[0], n = 1.  s >= 1 and lit != lit_prev: f = g_prev / (g_prev - g); if !(f >= 0 &&   */
+/*     f <= 1) f = 0.5; tau = times[s-1] + f * (times[s] - times[s-1]), every operation float64 and rounded on its own; up:         */
+/*     open = tau, if n == 0 rise = tau, n += 1; down: dur += tau - open, set = tau.  After the last position, if lit:             */
+/*     dur += times[num_sun-1] - open, set = times[num_sun-1].                                                                    */
+/*   sunrise = (float)rise, sunset = (float)set, duration = (float)dur (one rounding each), intervals = n.  Never lit: NaN, NaN,   */
+/*   0.0f, 0.  Masked cells (mask != 1): sw_dir_cor_fill in the three float maps, -1 in intervals.                                 */
+/* Both horizon layouts give the same words, and the position chunk ("horisun_chunk") changes none.  Any subset of the four        */
+/* outputs f32 / i32 [dim_in_0][dim_in_1] (at least one; NULL = not wanted; all different); positions, times and outputs may be    */
+/* host or device pointers.  Between the launches of a call the running state lives in 44 B per cell; a call of one chunk needs    */
+/* none.  stats (may be NULL): t_kernel_s, t_d2h_s, t_total_s, num_cells, scratch_bytes = that state plus staging; it does not     */
+/* grow with num_sun                                                                                                             */
+typedef struct hz_suntimes_out {
+    int32_t size;            /* sizeof(hz_suntimes_out) */
+    float*   sunrise;        /* f32[y][x], optional */
+    float*   sunset;         /* f32[y][x], optional */
+    float*   duration;       /* f32[y][x], optional */
+    int32_t* intervals;      /* i32[y][x], optional */
+} hz_suntimes_out;
+int hz_horizon_terrain_sun_times(hz_horizon_terrain* t, const float* sun_positions, const double* times,
+        int num_sun, const hz_suntimes_out* out, hz_stats* stats);
 /* DESIGN.md section 4 clause 12: hz_terrain_sw_dir_cor_coarse from the stored horizon.  For position s and coarse cell       */
 /* (I, J), B = the cells (i, j), I * P0 <= i < (I + 1) * P0, J * P1 <= j < (J + 1) * P1, with mask[i][j] == 1, and n = |B|:     */
 /*   f_cor[s][I][J] = (float)(SUM / (double)n), SUM a float64 accumulator that starts at 0.0 and takes (double)v one cell at a   */
