@@ -793,6 +793,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     auto fail = [&](int code) { (void)hipStreamSynchronize(st); if (st_copy) (void)hipStreamSynchronize(st_copy); free_events(); return code; };
     int n_chunk = 0;
     unsigned long long left_cells = 0, left_again = 0;
+    unsigned long long lend_tests = 0, lend_unhelped = 0;      // counting instantiation with leaf lending (hz_trace)
     float ms_left = 0.0f;
     for (int rb = row_begin; rb < row_end; rb += chunk_rows, n_chunk++) {
         const int re = std::min(rb + chunk_rows, row_end);
@@ -936,6 +937,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
             for (int k = 0; k < 16; k++) cnt[k] += c[k];
             left_cells += c[28]; left_again += c[29];
             n_verified += c[21];
+            lend_tests += c[22]; lend_unhelped += c[23];
             if (a.count_work && opts && opts->verbose >= 3) {      // per-XCD span of this launch (counting instantiation)
                 const unsigned long long t0 = ~c[20];
                 fprintf(stderr, "hz xcd spans [ms] rows %d..%d:", rb, re);
@@ -977,6 +979,10 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
         stats->height_field = height_field ? 1 : 0; stats->near_used = use_near ? 1 : 0;
     }
     if (near_reasons) print_near_reasons(near_reasons);
+    if (a.count_work && opts && opts->verbose >= 2 && lend_tests + lend_unhelped > 0)      // (a launch with leaf lending ran)
+        fprintf(stderr, "hz leaf lending: %llu lent leaf tests, %llu leaf-step lanes with a second leaf and no helper (a = %.3f); "
+                        "wave leaf steps %llu, wave node steps %llu, triangles tested %llu\n", lend_tests, lend_unhelped,
+                (lend_tests + lend_unhelped) ? (double)lend_tests / (double)(lend_tests + lend_unhelped) : 0.0, cnt[6], cnt[5], cnt[3]);
     if (opts && opts->verbose)
         print_reference_report(sc, alg, cnt[4], cnt[0], slab_cells, dim_in_0, dim_in_1, azim_num, (double)ms * 1e-3,
                                !use_near && near_opt <= 0 && !height_field && !bad_map, use_near && bad_map);
@@ -1584,6 +1590,7 @@ int hz_debug_set(const char *key, int value) {
     if (!key) return hz::set_error(HZ_ERR_ARG, "hz_debug_set: null key");
     if (!strcmp(key, "shadow_fast_cap")) hz::g_shadow_fast_cap.store(value < 0 ? HZ_SHADOW_FAST_CAP_DEFAULT : value, std::memory_order_relaxed);
     else if (!strcmp(key, "topo_wide")) hz::g_topo_wide.store(value != 0, std::memory_order_relaxed);
+    else if (!strcmp(key, "leaf_lend")) hz::g_leaf_lend.store(value != 0, std::memory_order_relaxed);      // (< 0: the default, on)
     else if (!strcmp(key, "accum_chunk")) hz::g_accum_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "coarse_tile")) hz::g_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_chunk")) hz::g_horisun_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);

@@ -103,7 +103,9 @@ __device__ __forceinline__ void hz_left_write(unsigned *w, unsigned cert, unsign
 // LEFT: the leftover instantiation (p.left_mode): a wave takes 64 records of cells that production blocks left unfinished instead of
 // an 8 x 8 block.  A template parameter and not a run-time switch: the restore code in front of the main loop cost the production
 // kernel 5 % (two rematerialised instructions in the node step, scratch reloads in the refill) although it never ran there.
-template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEFT = false>
+// LEND: leaf lending in the traversal's leaf step (hz_trace; fast stack only).  A template parameter chosen at launch
+// (hz_debug_set("leaf_lend", 0 | 1), default 1): the instantiation without it is the same-library A/B and the tests' reference.
+template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEFT = false, bool LEND = false>
 #ifndef HZ_WG_PER_CU
 #define HZ_WG_PER_CU 5     // resident workgroups per CU the register allocation is held to (6: 80 VGPRs, measured slower)
 #endif
@@ -280,6 +282,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     s.lim_up = 0; s.lim_low = 0; s.elev_samp = 0; s.ev = 0;
     unsigned rays = 0, guards = 0, w_adv = 0;
     TravCounters tc; tc.nodes = 0; tc.tris = 0; tc.w_nodes = 0; tc.w_leaves = 0;   // COUNT only
+    LendCounters lc; lc.lent = 0; lc.unhelped = 0;                                  // COUNT && LEND only
     const unsigned cells_cnt = (in_dom && !done && !LEFT) ? 1u : 0u;
     bool ray_active = false, last_hit = false;
     float dx = 0, dy = 0, dz = 1;
@@ -414,8 +417,8 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
         bool start_v = false, viol = false;
         if (ray_active) {
             int r;
-            r = hz_trace<HZ_TPB, COUNT, HZ_QLEN, NODELET, LEVELSTACK>(p.sv.nodes, p.sv.prims, top, ntop, stack, tid, ox, oy, oz,
-                                                 dx, dy, dz, tfar, p.dist_box, rb, ts, p.regroup, p.leaf_bias, tc, p.stack_cap, overflow);
+            r = hz_trace<HZ_TPB, COUNT, HZ_QLEN, NODELET, LEVELSTACK, LEND>(p.sv.nodes, p.sv.prims, top, ntop, stack, tid, ox, oy, oz,
+                                                 dx, dy, dz, tfar, p.dist_box, rb, ts, p.regroup, p.leaf_bias, tc, p.stack_cap, overflow, &lc);
             if (r == 0 && second) {                      // nothing in the cached subtree: full traversal
                 second = false; hz_trav_reset(ts);
             } else if (COUNT && want_v && r != 2) {
@@ -438,11 +441,13 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     // one atomic per wave and counter
     unsigned long long r = rays, g = guards, nc = tc.nodes, tcn = tc.tris, cc = cells_cnt;
     unsigned long long wn = tc.w_nodes, wl = tc.w_leaves, wa = w_adv;
+    unsigned long long ln = lc.lent, un = lc.unhelped;
     for (int off = 32; off > 0; off >>= 1) {
         r += __shfl_xor(r, off); g += __shfl_xor(g, off); cc += __shfl_xor(cc, off);
         if (COUNT) {
             nc += __shfl_xor(nc, off); tcn += __shfl_xor(tcn, off);
             wn += __shfl_xor(wn, off); wl += __shfl_xor(wl, off); wa += __shfl_xor(wa, off);
+            if (LEND) { ln += __shfl_xor(ln, off); un += __shfl_xor(un, off); }
         }
     }
     // !LEVELSTACK: a wave in which a ray ran out of stack entries does not count; its block is computed again by the
@@ -463,6 +468,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
         if (COUNT) {
             atomicAdd(&p.counters[2], nc); atomicAdd(&p.counters[3], tcn);
             atomicAdd(&p.counters[5], wn); atomicAdd(&p.counters[6], wl); atomicAdd(&p.counters[7], wa);
+            if (LEND) { atomicAdd(&p.counters[22], ln); atomicAdd(&p.counters[23], un); }
         }
     }
     if (COUNT) {
@@ -488,6 +494,8 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
   }     // next block of this wave
 }
 
+std::atomic<int> g_leaf_lend{1};      // hz_debug_set("leaf_lend", 0 | 1) (hz_internal.h)
+
 // Workgroups of `func` (HZ_TPB threads, `lds` bytes of dynamic LDS) the current device keeps resident at once; 0: unknown.  Asked once
 // per (kernel, LDS size, device): the occupancy query and hipGetDeviceProperties are host-side work in front of every launch otherwise.
 static long long resident_workgroups(const void *func, size_t lds) {
@@ -509,9 +517,9 @@ static long long resident_workgroups(const void *func, size_t lds) {
     return n;
 }
 
-template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK>
+template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEND = false>
 static int launch_one(const HorizonParams &p_in, int grid, size_t lds, int persist_grid, hipStream_t st) {
-    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK>);
+    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK, false, LEND>);
     HZ_HIP(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HorizonParams p = p_in;
     if (p.persist) {
@@ -525,7 +533,7 @@ static int launch_one(const HorizonParams &p_in, int grid, size_t lds, int persi
             HZ_HIP(hipMemsetAsync(p.queue, 0, 8 * sizeof(unsigned), st));
         }
     }
-    hipLaunchKernelGGL((k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK>), dim3(grid), dim3(HZ_TPB), lds, st, p);
+    hipLaunchKernelGGL((k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK, false, LEND>), dim3(grid), dim3(HZ_TPB), lds, st, p);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }
@@ -533,14 +541,14 @@ static int launch_one(const HorizonParams &p_in, int grid, size_t lds, int persi
 // The LEFT instantiation: always persistent -- how many records there are is only known on the device (left_in_ctl), so the launch has
 // the resident number of workgroups and every wave pulls groups of 64 sorted records until none is left.
 // (with a list -- the groups to repeat after a stack overflow -- one group per wave of a plain launch)
-template <int ALG, bool STAGE, bool LS>
+template <int ALG, bool STAGE, bool LS, bool LEND = false>
 static int launch_left(const HorizonParams &p, size_t lds, int persist_grid, hipStream_t st) {
-    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, false, STAGE, false, LS, true>);
+    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, false, STAGE, false, LS, true, LEND>);
     HZ_HIP(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     long long grid = p.tile_list ? (long long)((p.n_list + HZ_WPB - 1) / HZ_WPB)
                                  : (persist_grid > 0 ? (long long)persist_grid : resident_workgroups(func, lds));
     if (grid <= 0) grid = 1024;
-    hipLaunchKernelGGL((k_horizon<ALG, false, STAGE, false, LS, true>), dim3((unsigned)grid), dim3(HZ_TPB), lds, st, p);
+    hipLaunchKernelGGL((k_horizon<ALG, false, STAGE, false, LS, true, LEND>), dim3((unsigned)grid), dim3(HZ_TPB), lds, st, p);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }
@@ -596,8 +604,12 @@ int left_sort(const HorizonArgs &a, int r, hipStream_t st) {
 template <int ALG>
 static int launch_alg(const HorizonParams &p, int grid, size_t lds, bool count, bool level_stack, int pg, hipStream_t st) {
     const bool stage = p.stage_bytes != 0;
+    // leaf lending (hz_trace): the fast stack's production, follow-up and counting instantiations; the level-stack fallback and the
+    // opt-in nodelet variant stay without it
+    const bool lend = !level_stack && g_leaf_lend.load(std::memory_order_relaxed) != 0;
     if (p.left_mode) {
         if (level_stack) return stage ? launch_left<ALG, true, true>(p, lds, pg, st) : launch_left<ALG, false, true>(p, lds, pg, st);
+        if (lend) return stage ? launch_left<ALG, true, false, true>(p, lds, pg, st) : launch_left<ALG, false, false, true>(p, lds, pg, st);
         return stage ? launch_left<ALG, true, false>(p, lds, pg, st) : launch_left<ALG, false, false>(p, lds, pg, st);
     }
     if (ALG == ALG_GUESS && !count && p.top_nodes > 0) {    // opt-in LDS nodelet variant (opts.top_nodes > 0)
@@ -609,6 +621,10 @@ static int launch_alg(const HorizonParams &p, int grid, size_t lds, bool count, 
     if (level_stack) {
         if (count) return stage ? launch_one<ALG, true, true, false, true>(p, grid, lds, pg, st) : launch_one<ALG, true, false, false, true>(p, grid, lds, pg, st);
         return stage ? launch_one<ALG, false, true, false, true>(p, grid, lds, pg, st) : launch_one<ALG, false, false, false, true>(p, grid, lds, pg, st);
+    }
+    if (lend) {
+        if (count) return stage ? launch_one<ALG, true, true, false, false, true>(p, grid, lds, pg, st) : launch_one<ALG, true, false, false, false, true>(p, grid, lds, pg, st);
+        return stage ? launch_one<ALG, false, true, false, false, true>(p, grid, lds, pg, st) : launch_one<ALG, false, false, false, false, true>(p, grid, lds, pg, st);
     }
     if (count) return stage ? launch_one<ALG, true, true, false, false>(p, grid, lds, pg, st) : launch_one<ALG, true, false, false, false>(p, grid, lds, pg, st);
     return stage ? launch_one<ALG, false, true, false, false>(p, grid, lds, pg, st) : launch_one<ALG, false, false, false, false>(p, grid, lds, pg, st);

@@ -27,6 +27,7 @@ int set_error(int code, const char *fmt, ...);
 #define HZ_SHADOW_FAST_CAP_DEFAULT 19   // entries of k_shadow_refill's fast stack (hz_shadow.hip)
 // test knobs (hz_debug_set, include/horayzon_hip.h): process wide, read at every launch; results never depend on them
 extern std::atomic<int> g_shadow_fast_cap;   // entries of k_shadow_refill's fast stack (default HZ_SHADOW_FAST_CAP_DEFAULT; 0: level stack only)
+extern std::atomic<int> g_leaf_lend;         // 1 (default): k_horizon's fast stack lends idle lanes to the partner lane's second queued leaf (hz_trace, LEND)
 extern std::atomic<int> g_topo_wide;         // 1: the reductions over the azimuth axis use the fallback kernel k_topo_wide
 extern std::atomic<int> g_accum_chunk;       // > 0: sun positions per chunk of hz_terrain_accumulate (default 0: from the memory budget)
 extern std::atomic<int> g_coarse_tile;       // > 0: cells of k_coarse_reduce's LDS tile, at most the default (hz_subgrid.hip; default 0)
@@ -160,6 +161,7 @@ struct HorizonArgs {
                                          // [5..7] wave iterations, [8] waves whose fast-discipline stack overflowed,
                                          // [9] rays shortened by a certificate, [10] certificate violations (verify), [11] cells with a guard event,
                                          // [21] shortened rays that were re-traced (verify);
+                                         // [22] leaf tests done by a partner lane, [23] leaf-step lanes with a second leaf and no helper (leaf lending, counting instantiation);
                                          // [24..27] = unsigned[8]: the per-XCD block queues of a persistent launch (hz_horizon.hip; zeroed by horizon_launch);
                                          // [HZ_CNT_LEFT ..): unsigned[HZ_LEFT_LEVELS][16], the control words of the leftover regions: [r][0] = slots
                                          // allocated in region r, [r][1] = valid records (k_left_keys), [r][8 + x] = groups of 64 handed to XCD x

@@ -95,7 +95,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     scene=None, svf_vec_tilt=None, svf_only=False, rows=None, count_work=False, devices=None,
                     topo=None, topo_vec_tilt=None, topo_only=False, layout="cell_major",
                     _top_nodes=-1, _regroup=-1, _hit_cache=True, _chunk_rows=0, _near_skip=True, _level_stack=False,
-                    _verify_near=False, _left_min=0, _persist_grid=0):
+                    _verify_near=False, _left_min=0, _persist_grid=0, _verbose=0):
     """Horizon computation for gridded domain.
 
     Parameters, units and return values are those of the reference
@@ -201,7 +201,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
 
     opts = hz_opts()
     opts.device = device
-    opts.verbose = int(bool(verbose))
+    opts.verbose = max(int(bool(verbose)), int(_verbose))      # _verbose = 2, 3: diagnostics of the library to stderr
     opts.top_nodes = _top_nodes
     opts.regroup = _regroup
     opts.no_hit_cache = 0 if _hit_cache else 1

@@ -351,7 +351,8 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* of the LDS tile of hz_terrain_sw_dir_cor_coarse's reduction (<= 0 or above the default: the default; blocks wider than the  */
 /* tile take the kernel without LDS), "horisun_chunk" = sun positions per launch of hz_horizon_terrain_run (<= 0: the default), */
 /* "horisun_coarse_route" / "horisun_coarse_tile": see hz_horizon_terrain_sw_dir_cor_coarse (< 0: the default),                 */
-/* "planes_chunk" = cells per staging chunk of hz_hori_to_planes / _from_planes / hz_topo_params_planes (<= 0: the default)    */
+/* "planes_chunk" = cells per staging chunk of hz_hori_to_planes / _from_planes / hz_topo_params_planes (<= 0: the default),   */
+/* "leaf_lend" = 0: the horizon kernel's fast stack runs without leaf lending (1 or < 0: the default, with it)                  */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */

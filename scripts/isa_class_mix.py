@@ -26,7 +26,7 @@ FAST = ("v_mul_f32", "v_fma_f32", "v_fmac_f32", "v_add_f32", "v_sub_f32", "v_sub
         "v_and_b32", "v_or_b32", "v_xor_b32", "v_not_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_add_co_u32",
         "v_addc_co_u32", "v_sub_co_u32", "v_subb_co_u32", "v_cndmask_b32", "v_lshlrev_b32", "v_lshrrev_b32",
         "v_ashrrev_i32", "v_bfe_u32", "v_bfe_i32", "v_and_or_b32", "v_or3_b32", "v_mul_u32_u24", "v_mad_u32_u24")
-KERNEL = "_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb0EEEvNS_13HorizonParamsE"     # <ALG_GUESS, !COUNT, STAGE, !NODELET, !LEVELSTACK, !LEFT>
+KERNEL = "_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb0ELb1EEEvNS_13HorizonParamsE"     # <ALG_GUESS, !COUNT, STAGE, !NODELET, !LEVELSTACK, !LEFT, LEND>
 
 
 def classify(lines):
@@ -91,7 +91,7 @@ def main():
     while i < len(k):
         if "#ASMSTART" in k[i]:
             j = next(q for q in range(i, len(k)) if "#ASMEND" in k[q])
-            blocks.append((i, j, sum("global_load_dwordx4" in x for x in k[i:j])))
+            blocks.append((i, j, sum("global_load_dwordx4" in x for x in k[i:j]), any("_dpp" in x for x in k[i:j])))
             i = j
         i += 1
     node = next(x for x in blocks if x[2] == 2)                      # 32 B node: two 16 B loads (three for the 48 B node of early round 4, four before)
@@ -115,7 +115,12 @@ def main():
             if cnt >= n_leaf:
                 leaf_end = i + 1
                 break
-    sec = {"node_step": k[node[1]:leaf[0]], "leaf_step": k[leaf[1]:leaf_end], "refill_and_loop_overhead": k[outer:hdr]}
+    # leaf lending (hz_trace<..., LEND>): the leaf step starts with the partner exchange, an asm block of DPP instructions in
+    # front of the leaf load -- the node step ends there, and the exchange counts as leaf step
+    lend = next((x for x in blocks if x[3] and node[0] < x[0] < leaf[0]), None)
+    leaf_head = k[lend[0]:leaf[0]] if lend else []
+    sec = {"node_step": k[node[1]:(lend[0] if lend else leaf[0])], "leaf_step": leaf_head + k[leaf[1]:leaf_end],
+           "refill_and_loop_overhead": k[outer:hdr]}
     res = {"kernel_asm_sha": bench.kernel_asm_sha(), "classes": "fast: " + ", ".join(FAST)}
     for name, lines in sec.items():
         f, s, names = classify(lines)

@@ -71,7 +71,8 @@ def assemblies(tree):
 
 
 # the kernels the counter files under profiles/ describe: production launch of k_horizon, its follow-up launch, the shadow kernel
-PROFILED = ("_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb0EEEvNS_13HorizonParamsE", "_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb1EEEvNS_13HorizonParamsE",
+# (k_horizon<..., LEFT, LEND>: the instantiations with leaf lending, which is what a launch takes by default)
+PROFILED = ("_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb0ELb1EEEvNS_13HorizonParamsE", "_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb1ELb1EEEvNS_13HorizonParamsE",
             "_ZN2hz15k_shadow_refillILb0ELb1EEEvNS_12ShadowParamsE")
 
 

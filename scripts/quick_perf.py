@@ -29,6 +29,9 @@ ap.add_argument("--verify-near", action="store_true")
 ap.add_argument("--left", type=lambda x: int(x, 0), default=0, help="hz_opts.left_min: byte l = hand-over threshold of level l (0: default, -1: off)")
 ap.add_argument("--pgrid", type=int, default=0, help="hz_opts.persist_grid")
 ap.add_argument("--tune", type=lambda x: int(x, 0), default=0, help="hz_opts.left_tune")
+ap.add_argument("--lend", type=int, default=-1, help="hz_debug_set(\"leaf_lend\", 0 | 1): leaf lending in the leaf step (-1: the default, on)")
+ap.add_argument("--rows", type=int, default=0, help="only the middle ROWS rows of the window")
+ap.add_argument("--verbose", type=int, default=0, help="hz_opts.verbose (2: diagnostics of the counting instantiation to stderr)")
 ap.add_argument("--verify-sample", type=int, default=0, help="production kernel with the sampled certificate check: one of every N shortened rays")
 args = ap.parse_args()
 
@@ -40,13 +43,17 @@ off = (n - w) // 2
 vec_norm, vec_north = synth.planar_frames(w, w)
 t = time.time()
 hz.horizon.schedule_overrides["left_tune"] = args.tune
+if args.lend >= 0:
+    from horayzon_amd import _lib
+    _lib.check(_lib.lib().hz_debug_set(b"leaf_lend", args.lend))
+rows = ((w - args.rows) // 2, (w - args.rows) // 2 + args.rows) if 0 < args.rows < w else None
 sc = hz.Scene.create(g["vert_grid"], n, n)
 print("scene create %.2fs" % (time.time() - t), json.dumps(sc.stats), flush=True)
 for rep in range(args.reps):
     t = time.time()
     hori, azim = hz.horizon.horizon_gridded(g["vert_grid"], n, n, vec_norm, vec_north, off, off,
                                             args.dist, azim_num=args.azim, ray_algorithm=args.alg,
-                                            scene=sc, _top_nodes=args.top, _regroup=args.regroup, _hit_cache=args.hit_cache, _near_skip=not args.no_near, _level_stack=(-args.stack if args.stack > 0 else False), _verify_near=(args.verify_sample if args.verify_sample else args.verify_near), _left_min=args.left, _persist_grid=args.pgrid, count_work=args.count_all or (args.count and rep == args.reps - 1))
+                                            scene=sc, rows=rows, _verbose=args.verbose, _top_nodes=args.top, _regroup=args.regroup, _hit_cache=args.hit_cache, _near_skip=not args.no_near, _level_stack=(-args.stack if args.stack > 0 else False), _verify_near=(args.verify_sample if args.verify_sample else args.verify_near), _left_min=args.left, _persist_grid=args.pgrid, count_work=args.count_all or (args.count and rep == args.reps - 1))
     st = hz.horizon.last_stats
     print("rep %d wall %.2fs kernel %.3fs rays %d rays/(cell*az) %.2f Mray/s %.1f cells/s %.0f nodes/ray %.1f tris/ray %.1f"
           % (rep, time.time() - t, st["t_kernel_s"], st["num_rays"], st["num_rays"] / (w * w * args.azim),
