@@ -1591,6 +1591,7 @@ int hz_debug_set(const char *key, int value) {
     if (!strcmp(key, "shadow_fast_cap")) hz::g_shadow_fast_cap.store(value < 0 ? HZ_SHADOW_FAST_CAP_DEFAULT : value, std::memory_order_relaxed);
     else if (!strcmp(key, "topo_wide")) hz::g_topo_wide.store(value != 0, std::memory_order_relaxed);
     else if (!strcmp(key, "leaf_lend")) hz::g_leaf_lend.store(value != 0, std::memory_order_relaxed);      // (< 0: the default, on)
+    else if (!strcmp(key, "flat_refill")) hz::g_flat_refill.store(value != 0, std::memory_order_relaxed);  // (< 0: the default, on)
     else if (!strcmp(key, "accum_chunk")) hz::g_accum_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "coarse_tile")) hz::g_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_chunk")) hz::g_horisun_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);

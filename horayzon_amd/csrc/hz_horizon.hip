@@ -105,7 +105,9 @@ __device__ __forceinline__ void hz_left_write(unsigned *w, unsigned cert, unsign
 // kernel 5 % (two rematerialised instructions in the node step, scratch reloads in the refill) although it never ran there.
 // LEND: leaf lending in the traversal's leaf step (hz_trace; fast stack only).  A template parameter chosen at launch
 // (hz_debug_set("leaf_lend", 0 | 1), default 1): the instantiation without it is the same-library A/B and the tests' reference.
-template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEFT = false, bool LEND = false>
+// FLAT: the refill of guess_constant as one branch-free pass (advance_guess_flat, hz_search.h) instead of the state machine's if-chain.
+// Chosen at launch like LEND (hz_debug_set("flat_refill", 0 | 1), default 1), for the instantiations that have LEND.
+template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEFT = false, bool LEND = false, bool FLAT = false>
 #ifndef HZ_WG_PER_CU
 #define HZ_WG_PER_CU 5     // resident workgroups per CU the register allocation is held to (6: 80 VGPRs, measured slower)
 #endif
@@ -161,6 +163,8 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
 #define HZ_KEEP(x) asm volatile("" : "+s"(x))
     HZ_KEEP(p.leaf_bias); HZ_KEEP(p.regroup); HZ_KEEP(p.neg_tau); HZ_KEEP(p.sv.cx); HZ_KEEP(p.sv.cy); HZ_KEEP(p.sv.cz);
     HZ_KEEP(p.near_idx); HZ_KEEP(p.near_r);
+    // (the flat follow-up instantiation: without these the node and the leaf step each re-load the scene's pointers from the argument segment)
+    if (FLAT && LEFT) { HZ_KEEP(p.sv.nodes); HZ_KEEP(p.sv.prims); }
 #undef HZ_KEEP
     int ti = 0, tj = 0;
     int blk = (int)blockIdx.x * HZ_WPB + wave;
@@ -367,6 +371,56 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
             unsigned cert_r = cert;
             asm volatile("" : "+v"(cert_r));
             out.hori = COUNT ? hori0 + (size_t)(cert_r * cell_stride) * (size_t)t.azim_num : hori0 + (size_t)cert_r * (size_t)t.azim_num;
+            // (the set-up of the new ray behind its loads, shared by the two forms of the refill.  GO: the lane has a next ray.)
+#define HZ_RAY_SETUP(GO) \
+                const float rx = ec * asn, ry = ec * acs, rz = es; \
+                float nx_ = r01, ny_ = r11, nz_ = r21;        /* (the empty asm keeps the products inside the loop) */ \
+                asm volatile("" : "+v"(nx_), "+v"(ny_), "+v"(nz_)); \
+                const float r00 = ny_ * r22 - nz_ * r12;      /* east = north x norm (horizon_comp.cpp:763-766) */ \
+                const float r10 = nz_ * r02 - nx_ * r22; \
+                const float r20 = nx_ * r12 - ny_ * r02; \
+                dx = (r00 * rx + r01 * ry) + r02 * rz; \
+                dy = (r10 * rx + r11 * ry) + r12 * rz; \
+                dz = (r20 * rx + r21 * ry) + r22 * rz; \
+                    tn = (s.ind >= near_i) ? near_rad : p.neg_tau;    /* no certificate: the box tests start at -tau (hz_common.h) */ \
+                if (COUNT && (GO) && tn > 0.0f) shortened++; \
+                if (COUNT) want_v = (GO) && p.verify_near && tn > 0.0f && (((rays + cert) & p.verify_mask) == 0u); \
+                HZ_OC(ocx, ocy, ocz) \
+                rb = hz_raybox(ocx + tn * dx, ocy + tn * dy, ocz + tn * dz, dx, dy, dz); \
+                hz_trav_reset(ts); \
+                /* a ray below the previous azimuth's horizon is expected to be blocked near the same ridge */ \
+                second = p.hit_cache && (cache != 0) && (s.ind <= s.pazim) && (s.k > 0); \
+                if (second) { \
+                    ts.node = cache; \
+                    /* Fast stack (round 5): the ROOT waits in entry 1, below the cached subtree.  A cache walk that finds nothing \
+                       pops it and carries on with the full traversal inside hz_trace -- the same node visits and triangle tests \
+                       as leaving the loop with "miss" and coming back with a reset state (which is what `second` still does for \
+                       the level stack, whose entries cannot name the root), but the lane does not idle until its wave leaves. \
+                       Depth: the walk below the cached node needs <= 3 * anc_levels entries above this one, far below the \
+                       root traversal's own maximum, so no launch overflows that did not before. */ \
+                    if (!LEVELSTACK) { ts.sp = 1; stack[HZ_TPB + tid] = 0; second = false; } \
+                }
+            if (FLAT) {
+                // the refill without a branch per search phase (hz_search.h): the azimuth's table entries and the certificate are
+                // asked for as soon as the next azimuth is known -- together with the midpoint pair --, the elevation's entries
+                // once that pair is there: two memory round trips.  Every lane of the refill runs the set-up; a lane whose cell
+                // is finished (GO false) computes a ray it never traces.
+                float ec = 0.0f, es = 0.0f, asn = 0.0f, acs = 0.0f, near_rad = 0.0f;
+                int near_i = 0x7fffffff;
+                const bool go = advance_guess_flat<STAGE>(s, last_hit, t, out, guards,
+                    [&](int kc) {
+                        asn = t.azim_sin[kc]; acs = t.azim_cos[kc];
+                        if (p.near_idx != nullptr) {
+                            near_i = (int)p.near_idx[(size_t)cert_r * (size_t)t.azim_num + kc];
+                            near_rad = p.near_r[cert_r];
+                        }
+                    },
+                    [&](int ind) { ec = t.elev_cos[ind]; es = t.elev_sin[ind]; });
+                HZ_RAY_SETUP(go)
+                ray_active = go;
+                done = !go;
+                rays += go ? 1u : 0u;
+            } else
             if (advance<ALG, STAGE>(s, last_hit, t, out, guards)) {
                 // local direction (east, north, up) and rotation: horizon_comp.cpp:357-361, :55-62
                 // every load of the new ray is issued before the first one is used: the table entries, and the certificate of
@@ -380,38 +434,13 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
                     near_i = (int)p.near_idx[(size_t)cert_r * (size_t)t.azim_num + s.k];
                     near_rad = p.near_r[cert_r];
                 }
-                const float rx = ec * asn, ry = ec * acs, rz = es;
-                float nx_ = r01, ny_ = r11, nz_ = r21;        // (the empty asm keeps the products inside the loop)
-                asm volatile("" : "+v"(nx_), "+v"(ny_), "+v"(nz_));
-                const float r00 = ny_ * r22 - nz_ * r12;      // east = north x norm (horizon_comp.cpp:763-766)
-                const float r10 = nz_ * r02 - nx_ * r22;
-                const float r20 = nx_ * r12 - ny_ * r02;
-                dx = (r00 * rx + r01 * ry) + r02 * rz;
-                dy = (r10 * rx + r11 * ry) + r12 * rz;
-                dz = (r20 * rx + r21 * ry) + r22 * rz;
-                    tn = (s.ind >= near_i) ? near_rad : p.neg_tau;    // no certificate: the box tests start at -tau (hz_common.h)
-                if (COUNT && tn > 0.0f) shortened++;
-                if (COUNT) want_v = p.verify_near && tn > 0.0f && (((rays + cert) & p.verify_mask) == 0u);
-                HZ_OC(ocx, ocy, ocz)
-                rb = hz_raybox(ocx + tn * dx, ocy + tn * dy, ocz + tn * dz, dx, dy, dz);
-                hz_trav_reset(ts);
-                // a ray below the previous azimuth's horizon is expected to be blocked near the same ridge
-                second = p.hit_cache && (cache != 0) && (s.ind <= s.pazim) && (s.k > 0);
-                if (second) {
-                    ts.node = cache;
-                    // Fast stack (round 5): the ROOT waits in entry 1, below the cached subtree.  A cache walk that finds nothing
-                    // pops it and carries on with the full traversal inside hz_trace -- the same node visits and triangle tests
-                    // as leaving the loop with "miss" and coming back with a reset state (which is what `second` still does for
-                    // the level stack, whose entries cannot name the root), but the lane does not idle until its wave leaves.
-                    // Depth: the walk below the cached node needs <= 3 * anc_levels entries above this one, far below the
-                    // root traversal's own maximum, so no launch overflows that did not before.
-                    if (!LEVELSTACK) { ts.sp = 1; stack[HZ_TPB + tid] = 0; second = false; }
-                }
+                HZ_RAY_SETUP(true)
                 ray_active = true;
                 rays++;
             } else {
                 done = true;
             }
+#undef HZ_RAY_SETUP
         }
         // ---- traversal (hz_common.h: speculative while-while, one postponed leaf per lane) ------
         bool start_v = false, viol = false;
@@ -495,6 +524,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
 }
 
 std::atomic<int> g_leaf_lend{1};      // hz_debug_set("leaf_lend", 0 | 1) (hz_internal.h)
+std::atomic<int> g_flat_refill{1};    // hz_debug_set("flat_refill", 0 | 1) (hz_internal.h)
 
 // Workgroups of `func` (HZ_TPB threads, `lds` bytes of dynamic LDS) the current device keeps resident at once; 0: unknown.  Asked once
 // per (kernel, LDS size, device): the occupancy query and hipGetDeviceProperties are host-side work in front of every launch otherwise.
@@ -517,9 +547,9 @@ static long long resident_workgroups(const void *func, size_t lds) {
     return n;
 }
 
-template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEND = false>
+template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEND = false, bool FLAT = false>
 static int launch_one(const HorizonParams &p_in, int grid, size_t lds, int persist_grid, hipStream_t st) {
-    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK, false, LEND>);
+    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK, false, LEND, FLAT>);
     HZ_HIP(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HorizonParams p = p_in;
     if (p.persist) {
@@ -533,7 +563,7 @@ static int launch_one(const HorizonParams &p_in, int grid, size_t lds, int persi
             HZ_HIP(hipMemsetAsync(p.queue, 0, 8 * sizeof(unsigned), st));
         }
     }
-    hipLaunchKernelGGL((k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK, false, LEND>), dim3(grid), dim3(HZ_TPB), lds, st, p);
+    hipLaunchKernelGGL((k_horizon<ALG, COUNT, STAGE, NODELET, LEVELSTACK, false, LEND, FLAT>), dim3(grid), dim3(HZ_TPB), lds, st, p);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }
@@ -541,14 +571,14 @@ static int launch_one(const HorizonParams &p_in, int grid, size_t lds, int persi
 // The LEFT instantiation: always persistent -- how many records there are is only known on the device (left_in_ctl), so the launch has
 // the resident number of workgroups and every wave pulls groups of 64 sorted records until none is left.
 // (with a list -- the groups to repeat after a stack overflow -- one group per wave of a plain launch)
-template <int ALG, bool STAGE, bool LS, bool LEND = false>
+template <int ALG, bool STAGE, bool LS, bool LEND = false, bool FLAT = false>
 static int launch_left(const HorizonParams &p, size_t lds, int persist_grid, hipStream_t st) {
-    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, false, STAGE, false, LS, true, LEND>);
+    const void *func = reinterpret_cast<const void *>(k_horizon<ALG, false, STAGE, false, LS, true, LEND, FLAT>);
     HZ_HIP(hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     long long grid = p.tile_list ? (long long)((p.n_list + HZ_WPB - 1) / HZ_WPB)
                                  : (persist_grid > 0 ? (long long)persist_grid : resident_workgroups(func, lds));
     if (grid <= 0) grid = 1024;
-    hipLaunchKernelGGL((k_horizon<ALG, false, STAGE, false, LS, true, LEND>), dim3((unsigned)grid), dim3(HZ_TPB), lds, st, p);
+    hipLaunchKernelGGL((k_horizon<ALG, false, STAGE, false, LS, true, LEND, FLAT>), dim3((unsigned)grid), dim3(HZ_TPB), lds, st, p);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }
@@ -607,6 +637,16 @@ static int launch_alg(const HorizonParams &p, int grid, size_t lds, bool count, 
     // leaf lending (hz_trace): the fast stack's production, follow-up and counting instantiations; the level-stack fallback and the
     // opt-in nodelet variant stay without it
     const bool lend = !level_stack && g_leaf_lend.load(std::memory_order_relaxed) != 0;
+    // the flat refill (advance_guess_flat): guess_constant's instantiations with lending; leaf_lend = 0 launches the ones without either
+    if constexpr (ALG == ALG_GUESS) {
+        if (lend && g_flat_refill.load(std::memory_order_relaxed) != 0 && !(!p.left_mode && !count && p.top_nodes > 0)) {
+            if (p.left_mode) return stage ? launch_left<ALG_GUESS, true, false, true, true>(p, lds, pg, st) : launch_left<ALG_GUESS, false, false, true, true>(p, lds, pg, st);
+            if (count) return stage ? launch_one<ALG_GUESS, true, true, false, false, true, true>(p, grid, lds, pg, st)
+                                    : launch_one<ALG_GUESS, true, false, false, false, true, true>(p, grid, lds, pg, st);
+            return stage ? launch_one<ALG_GUESS, false, true, false, false, true, true>(p, grid, lds, pg, st)
+                         : launch_one<ALG_GUESS, false, false, false, false, true, true>(p, grid, lds, pg, st);
+        }
+    }
     if (p.left_mode) {
         if (level_stack) return stage ? launch_left<ALG, true, true>(p, lds, pg, st) : launch_left<ALG, false, true>(p, lds, pg, st);
         if (lend) return stage ? launch_left<ALG, true, false, true>(p, lds, pg, st) : launch_left<ALG, false, false, true>(p, lds, pg, st);

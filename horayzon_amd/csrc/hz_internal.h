@@ -28,6 +28,7 @@ int set_error(int code, const char *fmt, ...);
 // test knobs (hz_debug_set, include/horayzon_hip.h): process wide, read at every launch; results never depend on them
 extern std::atomic<int> g_shadow_fast_cap;   // entries of k_shadow_refill's fast stack (default HZ_SHADOW_FAST_CAP_DEFAULT; 0: level stack only)
 extern std::atomic<int> g_leaf_lend;         // 1 (default): k_horizon's fast stack lends idle lanes to the partner lane's second queued leaf (hz_trace, LEND)
+extern std::atomic<int> g_flat_refill;       // 1 (default): guess_constant's fast-stack instantiations refill through advance_guess_flat (hz_search.h, FLAT)
 extern std::atomic<int> g_topo_wide;         // 1: the reductions over the azimuth axis use the fallback kernel k_topo_wide
 extern std::atomic<int> g_accum_chunk;       // > 0: sun positions per chunk of hz_terrain_accumulate (default 0: from the memory budget)
 extern std::atomic<int> g_coarse_tile;       // > 0: cells of k_coarse_reduce's LDS tile, at most the default (hz_subgrid.hip; default 0)

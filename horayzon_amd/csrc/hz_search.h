@@ -162,4 +162,72 @@ __device__ __forceinline__ bool advance(Search &s, bool hit, const Tables &t, Si
     }
 }
 
+// advance<ALG_GUESS, STAGE> as one pass without a loop (k_horizon<..., FLAT>): the same transitions on the same Search encoding.
+// After azimuth 0 a guess_constant lane is in PH_UP or PH_DOWN whenever a ray ends, and what happens next is one of
+//   step on    UP with a hit below the top index, DOWN with a miss above index 0
+//   turn round UP with a miss (or a hit at the top) on the first sample
+//   finalize   everything else: the midpoint entry is emitted and azimuth k + 1 starts with its first UP sample
+// The three cases are 0 / -1 words in vector registers, combined with AND / OR / bit-select (the empty asm hides them from the
+// compiler's mask algebra, as in hz_trace: no scalar logic on vector compares, no exec-mask branch per case).  PH_BIN and PH_NEWAZ
+// (azimuth 0) run the state machine above behind a wave-uniform branch; so does the midpoint of a step that was clamped at a table
+// end.  PH_EMIT does not persist, as before.
+//   issue_k(k')     called once the azimuth of the next ray is known (k' <= azim_num - 1: a lane that finishes keeps the last one)
+//   issue_ind(ind') called once its table index is known
+// are where the caller issues the loads of the new ray, so that they are in flight together with / right behind the midpoint pair.
+#define HZ_HIDE(m) asm volatile("" : "+v"(m))
+#define HZ_BSEL(m, x, y) (((m) & (x)) | (~(m) & (y)))
+template <bool STAGE, class FK, class FI>
+__device__ __forceinline__ bool advance_guess_flat(Search &s, bool hit, const Tables &t, Sink &out, unsigned &guards,
+                                                   FK &&issue_k, FI &&issue_ind) {
+    const int top = t.elev_num - 1;
+    int m_flat = (int)((unsigned)s.phase << 30) >> 31;       // PH_UP = 2, PH_DOWN = 3: bit 1
+    HZ_HIDE(m_flat);
+    if (__ballot(m_flat == 0) != 0ull) {                     // azimuth 0 only: no lane takes this after the first rays of a block
+        if (m_flat == 0) (void)advance<ALG_GUESS, STAGE>(s, hit, t, out, guards);      // (false: s.k == azim_num, see the return below)
+    }
+    // ---- decide ----  (every case mask is inside m_flat: the lanes of the branch above keep the state it left)
+    int m_down = (int)((unsigned)s.phase << 31) >> 31;
+    int m_hit = hit ? -1 : 0;
+    int m_end = (s.ind == (top & ~m_down)) ? -1 : 0;         // at the index the phase cannot step beyond
+    int m_many = (1 - s.count) >> 31;                        // count > 1
+    HZ_HIDE(m_down); HZ_HIDE(m_hit); HZ_HIDE(m_end); HZ_HIDE(m_many);
+    const int m_fwd = (m_hit ^ m_down) & m_flat;             // the ray says "further": blocked on the way up, free on the way down
+    const int m_step = m_fwd & ~m_end;
+    const int m_turn = m_flat & ~(m_step | m_down | m_many);
+    const int m_fin = m_flat & ~(m_step | m_turn);
+    guards += (unsigned)(m_fwd & m_end & 1);                 // the reference never leaves this loop
+    // ---- the three successors ----
+    const int st_ind = min(max(s.ind + 10 - (20 & m_down), 0), top);
+    const int tu_prev = min(s.pazim + 5, top), tu_ind = max(tu_prev - 10, 0);
+    const int lo = min(s.prev, s.ind), hi = max(s.prev, s.ind);
+    const int2 pair = reinterpret_cast<const int2 *>(t.mid_idx)[min(max(lo, 0), top)];      // (all lanes: inside the table whatever the state)
+    int m_gen = (hi - lo != 10) ? m_fin : 0;                 // a step clamped at a table end: the general midpoint
+    HZ_HIDE(m_gen);
+    const int k_new = s.k - m_fin;
+    issue_k(min(k_new, t.azim_num - 1));                     // (k_new == azim_num: that was the cell's last azimuth)
+    int mid = pair.x, evb = pair.y;
+    if (__ballot(m_gen != 0) != 0ull) {
+        if (m_gen != 0) {
+            mid = ind_of(t, half_sum(t.elev_ang[s.prev], t.elev_ang[s.ind]));
+            evb = __float_as_int(t.elev_ang[mid]);
+        }
+    }
+    const int fi_prev = max(mid - 5, 0), fi_ind = min(fi_prev + 10, top);
+    const int ind_new = HZ_BSEL(m_step, st_ind, HZ_BSEL(m_turn, tu_ind, HZ_BSEL(m_fin, fi_ind, s.ind)));
+    issue_ind(ind_new);
+    const int k_emit = s.k;
+    s.prev = HZ_BSEL(m_step, s.ind, HZ_BSEL(m_turn, tu_prev, HZ_BSEL(m_fin, fi_prev, s.prev)));
+    s.ind = ind_new;
+    s.count = HZ_BSEL(m_fin, 1, s.count + (m_step & ~m_down & 1));
+    s.phase += m_turn & 1;                                   // UP -> DOWN
+    s.phase -= m_fin & m_down & 1;                           // DOWN -> UP (azimuth k + 1)
+    s.pazim = HZ_BSEL(m_fin, mid, s.pazim);
+    s.ev = __int_as_float(HZ_BSEL(m_fin, evb, __float_as_int(s.ev)));
+    s.k = k_new;
+    if (m_fin != 0) emit<STAGE>(out, t, k_emit, __int_as_float(evb));      // one exec-mask region: the lanes that finalize
+    return s.k < t.azim_num;
+}
+#undef HZ_BSEL
+#undef HZ_HIDE
+
 }  // namespace hz

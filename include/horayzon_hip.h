@@ -353,6 +353,8 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* "horisun_coarse_route" / "horisun_coarse_tile": see hz_horizon_terrain_sw_dir_cor_coarse (< 0: the default),                 */
 /* "planes_chunk" = cells per staging chunk of hz_hori_to_planes / _from_planes / hz_topo_params_planes (<= 0: the default),   */
 /* "leaf_lend" = 0: the horizon kernel's fast stack runs without leaf lending (1 or < 0: the default, with it)                  */
+/* "flat_refill" = 0: guess_constant's refill runs the search state machine's if-chain (1 or < 0: the default, the branch-free */
+/* pass; it belongs to the instantiations with leaf lending, so "leaf_lend" = 0 switches it off too)                            */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */

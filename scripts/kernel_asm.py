@@ -71,8 +71,8 @@ def assemblies(tree):
 
 
 # the kernels the counter files under profiles/ describe: production launch of k_horizon, its follow-up launch, the shadow kernel
-# (k_horizon<..., LEFT, LEND>: the instantiations with leaf lending, which is what a launch takes by default)
-PROFILED = ("_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb0ELb1EEEvNS_13HorizonParamsE", "_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb1ELb1EEEvNS_13HorizonParamsE",
+# (k_horizon<..., LEFT, LEND, FLAT>: the instantiations with leaf lending and the flat refill, which is what a launch takes by default)
+PROFILED = ("_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb0ELb1ELb1EEEvNS_13HorizonParamsE", "_ZN2hz9k_horizonILi2ELb0ELb1ELb0ELb0ELb1ELb1ELb1EEEvNS_13HorizonParamsE",
             "_ZN2hz15k_shadow_refillILb0ELb1EEEvNS_12ShadowParamsE")
 
 

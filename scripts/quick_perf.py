@@ -30,6 +30,7 @@ ap.add_argument("--left", type=lambda x: int(x, 0), default=0, help="hz_opts.lef
 ap.add_argument("--pgrid", type=int, default=0, help="hz_opts.persist_grid")
 ap.add_argument("--tune", type=lambda x: int(x, 0), default=0, help="hz_opts.left_tune")
 ap.add_argument("--lend", type=int, default=-1, help="hz_debug_set(\"leaf_lend\", 0 | 1): leaf lending in the leaf step (-1: the default, on)")
+ap.add_argument("--flat", type=int, default=-1, help="hz_debug_set(\"flat_refill\", 0 | 1): the branch-free refill of guess_constant (-1: the default, on)")
 ap.add_argument("--rows", type=int, default=0, help="only the middle ROWS rows of the window")
 ap.add_argument("--verbose", type=int, default=0, help="hz_opts.verbose (2: diagnostics of the counting instantiation to stderr)")
 ap.add_argument("--verify-sample", type=int, default=0, help="production kernel with the sampled certificate check: one of every N shortened rays")
@@ -46,6 +47,9 @@ hz.horizon.schedule_overrides["left_tune"] = args.tune
 if args.lend >= 0:
     from horayzon_amd import _lib
     _lib.check(_lib.lib().hz_debug_set(b"leaf_lend", args.lend))
+if args.flat >= 0:
+    from horayzon_amd import _lib
+    _lib.check(_lib.lib().hz_debug_set(b"flat_refill", args.flat))
 rows = ((w - args.rows) // 2, (w - args.rows) // 2 + args.rows) if 0 < args.rows < w else None
 sc = hz.Scene.create(g["vert_grid"], n, n)
 print("scene create %.2fs" % (time.time() - t), json.dumps(sc.stats), flush=True)

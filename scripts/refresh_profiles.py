@@ -23,8 +23,8 @@ try:      # config 4
     shutil.copy(src + "/%s_c4kt_bench.json" % pre, "profiles/%s/bench_c4_under_rocprof.json" % rnd)
 except (ValueError, OSError):
     pass
-KERNEL = "k_horizon<2, false, true, false, false, false, true>"      # the production instantiation
-LEFT = "k_horizon<2, false, true, false, false, true, true>"         # its follow-up launch (the cells handed over), fast stack
+KERNEL = "k_horizon<2, false, true, false, false, false, true, true>"      # the production instantiation
+LEFT = "k_horizon<2, false, true, false, false, true, true, true>"         # its follow-up launch (the cells handed over), fast stack
 
 
 def per_kernel(d, names):
