@@ -975,8 +975,12 @@ int scene_build(Scene *sc, const float *vert_grid, int d0, int d1,
     Prim *d_prims = (Prim *)(blob + h.off_prims);
     int *d_anc = (int *)(blob + h.off_anc);
     HZ_HIP(hipMemcpyAsync(d_verts, d_verts_src, nvert * 12, hipMemcpyDeviceToDevice, st));
-    // unused leaf slots stay zero (a collapsed triangle: den = 0, never a hit); unused node slots: k_fill_dead_nodes
-    HZ_HIP(hipMemsetAsync(blob + h.off_nodes, 0, h.total_bytes - h.off_nodes, st));
+    // unused leaf slots stay zero (a collapsed triangle: den = 0, never a hit); unused node slots: k_fill_dead_nodes.
+    // The clear starts right behind the vertices: the up to 255 bytes between them and the 256-aligned node array belong to
+    // no region, and left as hipMalloc handed them out two builds of one scene differed in those bytes (a blob is broadcast
+    // and compared byte for byte: tests/test_gpu_bvh_blob.py).
+    const size_t verts_end = h.off_verts + nvert * 12;
+    HZ_HIP(hipMemsetAsync(blob + verts_end, 0, h.total_bytes - verts_end, st));
     hipLaunchKernelGGL(k_fill_dead_nodes, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, st, d_nodes, n_nodes);
     if (want_bad_map && h.bad_sx > 0.0f && h.bad_sy > 0.0f) {
         TempBuf b_ovf;
