@@ -99,6 +99,8 @@ SYMBOLS = (
     "hz_horizon_gridded_planes", "hz_horizon_gridded_scene_planes", "hz_hori_to_planes", "hz_hori_from_planes",
     "hz_topo_params_planes", "hz_horizon_terrain_initialise_planes",
     "hz_horizon_terrain_sw_dir_cor_coarse", "hz_horizon_terrain_refraction", "hz_horizon_terrain_sun_times",
+    "hz_hori_quantise", "hz_hori_dequantise", "hz_horizon_gridded_q16", "hz_horizon_gridded_scene_q16",
+    "hz_horizon_terrain_initialise_q16",
 )
 
 
@@ -158,6 +160,13 @@ def lib():
                                                                                          C.POINTER(hz_stats)]
     L.hz_horizon_gridded_planes.argtypes = L.hz_horizon_gridded_ex.argtypes
     L.hz_horizon_gridded_scene_planes.argtypes = L.hz_horizon_gridded_scene_ex.argtypes
+    # the _q16 forms: `hori_q` in place of hori_planes and `int planes` after it
+    L.hz_horizon_gridded_q16.argtypes = (L.hz_horizon_gridded_ex.argtypes[:8] + [ip]
+                                         + L.hz_horizon_gridded_ex.argtypes[8:])
+    L.hz_horizon_gridded_scene_q16.argtypes = (L.hz_horizon_gridded_scene_ex.argtypes[:6] + [ip]
+                                               + L.hz_horizon_gridded_scene_ex.argtypes[6:])
+    L.hz_hori_quantise.argtypes = [vp, C.c_size_t, vp, ip]
+    L.hz_hori_dequantise.argtypes = [vp, C.c_size_t, vp, ip]
     L.hz_hori_to_planes.argtypes = [vp, ip, ip, ip, vp, ip]
     L.hz_hori_from_planes.argtypes = [vp, ip, ip, ip, vp, ip]
     L.hz_topo_params_planes.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp, vp, ip]
@@ -209,6 +218,8 @@ def lib():
     L.hz_horizon_terrain_initialise.argtypes = [vp, vp, ip, vp, ip, ip, ip, ip, vp, vp, vp, ip, ip, vp, vp,
                                                 C.c_float, C.c_float, C.POINTER(hz_stats)]
     L.hz_horizon_terrain_initialise_planes.argtypes = L.hz_horizon_terrain_initialise.argtypes
+    L.hz_horizon_terrain_initialise_q16.argtypes = (L.hz_horizon_terrain_initialise.argtypes[:3] + [ip]
+                                                    + L.hz_horizon_terrain_initialise.argtypes[3:])
     L.hz_horizon_terrain_run.argtypes = [vp, vp, vp, ip, C.POINTER(hz_horisun_out), C.POINTER(hz_stats)]
     L.hz_horizon_terrain_sw_dir_cor_coarse.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.POINTER(hz_stats)]
     L.hz_horizon_terrain_refraction.argtypes = [vp, vp, C.POINTER(hz_stats)]

@@ -549,7 +549,8 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
                        int offset_1, float *hori_buffer, int dim_in_0, int dim_in_1, int azim_num,
                        float dist_search, float hori_acc, const char *ray_algorithm,
                        float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
-                       const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats, float *hori_planes = nullptr) {
+                       const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats, float *hori_planes = nullptr,
+                       uint16_t *hori_q = nullptr, int q_planes = 0) {
     int alg = 2;
     int rc = parse_alg(ray_algorithm, &alg);
     if (rc) return rc;
@@ -562,9 +563,14 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     // hori_planes (hz_horizon_gridded_planes): the horizon leaves as planes[azim][y][x]; the cell-major horizon lives in the
     // chunk buffer of skip_hori only, and every chunk is transposed into its rows of every plane (hz_planes.hip)
     const bool to_planes = hori_planes != nullptr;
-    if (to_planes && skip_hori) return set_error(HZ_ERR_ARG, "skip_hori with hori_planes: there is nothing to lay out");
-    if (to_planes) hori_buffer = nullptr;
-    if (!hori_buffer && !skip_hori && !to_planes) return set_error(HZ_ERR_ARG, "hori_buffer is NULL");
+    // hori_q (hz_horizon_gridded_q16): the horizon leaves as 16-bit codes (hz_q16.hip), cell-major or (q_planes) as planes; the
+    // float32 horizon lives in the same chunk buffer, is reduced there (svf, topo) and then encoded into its place
+    const bool to_q16 = !to_planes && hori_q != nullptr;
+    const bool to_layout = to_planes || to_q16;
+    if (to_layout && skip_hori)
+        return set_error(HZ_ERR_ARG, "skip_hori with %s: there is nothing to lay out", to_q16 ? "hori_q" : "hori_planes");
+    if (to_layout) hori_buffer = nullptr;
+    if (!hori_buffer && !skip_hori && !to_layout) return set_error(HZ_ERR_ARG, "hori_buffer is NULL");
     if (opts && opts->svf && !opts->vec_tilt) return set_error(HZ_ERR_ARG, "opts.svf needs opts.vec_tilt");
     // the SVF weights sectors by azim[1] - azim[0] (topo_param.pyx:433): undefined for a single azimuth
     if (opts && opts->svf && azim_num < 2) return set_error(HZ_ERR_ARG, "opts.svf needs azim_num >= 2");
@@ -649,20 +655,24 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     size_t tmp_bytes = 0;         // chunk buffers of a host / skipped hori_buffer (hz_stats.scratch_bytes)
     struct TmpFree { void **p; ~TmpFree() { if (*p) (void)hipFree(*p); } } tmp_free{&tmp_hori}, tmp_free2{&tmp_hori2};
     const size_t row_bytes = (size_t)dim_in_1 * azim_num * 4;
-    const bool stream_out = !skip_hori && !to_planes && !is_device_ptr(hori_slab_host);
+    const bool stream_out = !skip_hori && !to_layout && !is_device_ptr(hori_slab_host);
     // planes: stride of one plane and the plane element of the slab's first cell, by the rules of hori_buffer
     const size_t plane_stride = hori_is_slab ? slab_cells : ncell;
     const size_t plane_cell0 = hori_is_slab ? 0 : (size_t)row_begin * dim_in_1;
     const bool planes_on_dev = to_planes && is_device_ptr(hori_planes);
     void *tmp_planes = nullptr;   // chunk of planes [azim_num][chunk cells] on its way to a host hori_planes
     TmpFree tmp_free3{&tmp_planes};
-    if (skip_hori || to_planes || stream_out) {
+    const bool q_on_dev = to_q16 && is_device_ptr(hori_q);
+    void *tmp_q = nullptr;        // chunk of codes, cell-major or [azim_num][chunk cells], on its way to a host hori_q
+    TmpFree tmp_free4{&tmp_q};
+    if (skip_hori || to_layout || stream_out) {
         if (skip_hori && !want_topo) return set_error(HZ_ERR_ARG, "skip_hori without svf, vsf or openness: nothing to compute");
         if ((rc = alloc_hori_chunk(row_end - row_begin, row_bytes, skip_hori, (opts && opts->chunk_rows > 0) ? opts->chunk_rows : 0, &chunk_rows, &tmp_hori)))
             return rc;
         tmp_bytes = (size_t)chunk_rows * row_bytes;
         if (stream_out && chunk_rows < row_end - row_begin) { HZ_HIP(hipMalloc(&tmp_hori2, (size_t)chunk_rows * row_bytes)); tmp_bytes *= 2; }
         if (to_planes && !planes_on_dev) { HZ_HIP(hipMalloc(&tmp_planes, (size_t)chunk_rows * row_bytes)); tmp_bytes *= 2; }
+        if (to_q16 && !q_on_dev) { HZ_HIP(hipMalloc(&tmp_q, (size_t)chunk_rows * (row_bytes / 2))); tmp_bytes += (size_t)chunk_rows * (row_bytes / 2); }
     } else {
         if ((rc = d_hori.bind(hori_slab_host, slab_cells * (size_t)azim_num))) return rc;
     }
@@ -720,7 +730,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     unsigned long long redo_blocks = 0, redo_groups = 0;
 
     // HIP events on the kernels' stream: horizon kernel and SVF kernel are timed separately
-    struct Ev { hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr, l = nullptr; };
+    struct Ev { hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr, l = nullptr, q = nullptr, r = nullptr; };
     std::vector<Ev> evs;          // one per launch attempt
     std::vector<size_t> ev_of;    // chunk -> its final attempt
     hipStream_t st_copy = nullptr;
@@ -731,6 +741,8 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
             if (e.c) (void)hipEventDestroy(e.c);
             if (e.d) (void)hipEventDestroy(e.d);
             if (e.l) (void)hipEventDestroy(e.l);
+            if (e.q) (void)hipEventDestroy(e.q);
+            if (e.r) (void)hipEventDestroy(e.r);
         }
         if (st_copy) { stream_release(sc->device, st_copy); st_copy = nullptr; }
     };
@@ -794,13 +806,13 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     int n_chunk = 0;
     unsigned long long left_cells = 0, left_again = 0;
     unsigned long long lend_tests = 0, lend_unhelped = 0;      // counting instantiation with leaf lending (hz_trace)
-    float ms_left = 0.0f;
+    float ms_left = 0.0f, ms_q_copy = 0.0f;
     for (int rb = row_begin; rb < row_end; rb += chunk_rows, n_chunk++) {
         const int re = std::min(rb + chunk_rows, row_end);
         // the kernels index hori by global cell: shift the (slab- or chunk-local) buffer back
         float *hori_chunk;
         if (stream_out) hori_chunk = (float *)((n_chunk & 1) ? tmp_hori2 : tmp_hori);
-        else if (skip_hori || to_planes) hori_chunk = (float *)tmp_hori;
+        else if (skip_hori || to_layout) hori_chunk = (float *)tmp_hori;
         else hori_chunk = d_hori.dev + (size_t)(rb - row_begin) * dim_in_1 * azim_num;
         a.hori = hori_chunk - (size_t)rb * dim_in_1 * azim_num;
         a.row_begin = rb; a.row_end = re;
@@ -923,6 +935,28 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
                         rc = set_error(HZ_ERR_HIP, "copy of the horizon planes failed: %s", hipGetErrorString(hipGetLastError()));
                 }
             }
+            if (!rc && to_q16) {
+                // the chunk as codes into its place: in place for a device hori_q, through the chunk buffer of codes and one
+                // copy for a host hori_q (planes: azim_num rows of the chunk's cells, pitch = plane stride; cell-major: plain)
+                const size_t cc = (size_t)(re - rb) * dim_in_1, c0 = plane_cell0 + (size_t)(rb - row_begin) * dim_in_1;
+                const size_t A = (size_t)azim_num;
+                uint16_t *tq = static_cast<uint16_t *>(tmp_q);
+                if (q_planes) rc = q_on_dev ? hori_quantise_planes_launch(hori_chunk, cc, azim_num, hori_q, plane_stride, c0, st)
+                                            : hori_quantise_planes_launch(hori_chunk, cc, azim_num, tq, cc, 0, st);
+                else rc = hori_quantise_launch(hori_chunk, cc * A, q_on_dev ? hori_q + c0 * A : tq, st);
+                if (!rc && !q_on_dev) {
+                    Ev &eq = evs.back();
+                    if (hipEventCreate(&eq.q) != hipSuccess || hipEventCreate(&eq.r) != hipSuccess)
+                        return fail(set_error(HZ_ERR_HIP, "hipEventCreate failed"));
+                    (void)hipEventRecord(eq.q, st);
+                    const hipError_t ce = q_planes
+                        ? hipMemcpy2DAsync(hori_q + c0, plane_stride * sizeof(uint16_t), tq, cc * sizeof(uint16_t),
+                                           cc * sizeof(uint16_t), A, hipMemcpyDeviceToHost, st)
+                        : hipMemcpyAsync(hori_q + c0 * A, tq, cc * A * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
+                    if (ce != hipSuccess) rc = set_error(HZ_ERR_HIP, "copy of the horizon codes failed: %s", hipGetErrorString(ce));
+                    (void)hipEventRecord(eq.r, st);
+                }
+            }
             if (!rc && stream_out && n_chunk >= 1) rc = copy_out(n_chunk - 1);
             if (rc) return fail(rc);
             unsigned long long c[HZ_CNT_N];
@@ -934,6 +968,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
             (void)hipEventElapsedTime(&m2, e.b, e.c);
             ms += m1; ms_svf += m2;
             if (evs.back().l) { float m3 = 0.0f; (void)hipEventElapsedTime(&m3, evs.back().l, e.b); ms_left += m3; }
+            if (evs.back().r) { float m4 = 0.0f; (void)hipEventElapsedTime(&m4, evs.back().q, evs.back().r); ms_q_copy += m4; }
             for (int k = 0; k < 16; k++) cnt[k] += c[k];
             left_cells += c[28]; left_again += c[29];
             n_verified += c[21];
@@ -968,7 +1003,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
         stats->nodes_visited += cnt[2]; stats->tris_tested += cnt[3]; stats->num_cells += cnt[4];
         stats->wave_node_iters += cnt[5]; stats->wave_leaf_iters += cnt[6]; stats->wave_refills += cnt[7];
         stats->t_h2d_s += h2d_s; stats->t_kernel_s += (double)ms * 1e-3; stats->t_svf_s += (double)ms_svf * 1e-3;
-        stats->t_d2h_s += d2h_s;
+        stats->t_d2h_s += d2h_s + (double)ms_q_copy * 1e-3;      // (the chunk copies of a host hori_q happen inside the loop)
         stats->t_total_s += t_total.stop();
         stats->elev_num = tb.elev_num; stats->bvh_height = sc->hdr.height; stats->scene_bytes = sc->hdr.total_bytes;
         stats->stack_fallbacks += (uint64_t)fallbacks; stats->stack_redo_blocks += redo_blocks; stats->left_redo_groups += redo_groups;
@@ -1201,6 +1236,29 @@ int hz_horizon_gridded_scene_planes(const hz_scene *scene, const float *vec_norm
                        elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, stats, hori_planes);
 }
 
+// hori_q u16[rows][dim_in_1][azim_num] or (planes) u16[azim_num][rows][dim_in_1] in place of hori_buffer: as check_planes_call
+static int check_q16_call(const uint16_t *hori_q, int planes, int dim_in_0, int dim_in_1, int azim_num, const hz_opts *opts) {
+    if (!hori_q) return set_error(HZ_ERR_ARG, "hori_q is NULL");
+    if (reinterpret_cast<uintptr_t>(hori_q) & 1) return set_error(HZ_ERR_ARG, "hori_q is not aligned to 2 bytes");
+    if (planes != 0 && planes != 1) return set_error(HZ_ERR_ARG, "planes must be 0 or 1");
+    if (dim_in_0 <= 0 || dim_in_1 <= 0 || azim_num <= 0) return set_error(HZ_ERR_ARG, "dim_in_0, dim_in_1 and azim_num must be positive");
+    if (opts && opts->skip_hori) return set_error(HZ_ERR_ARG, "skip_hori with hori_q: there is nothing to lay out");
+    return HZ_OK;
+}
+
+int hz_horizon_gridded_scene_q16(const hz_scene *scene, const float *vec_norm, const float *vec_north,
+                                 int offset_0, int offset_1, uint16_t *hori_q, int planes, int dim_in_0, int dim_in_1,
+                                 int azim_num, float dist_search, float hori_acc, const char *ray_algorithm,
+                                 float elev_ang_low_lim, const uint8_t *mask, float hori_fill,
+                                 float ray_org_elev, const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    if (!scene) return set_error(HZ_ERR_ARG, "scene is NULL");
+    const int rc = check_q16_call(hori_q, planes, dim_in_0, dim_in_1, azim_num, opts);
+    if (rc) return rc;
+    return horizon_run(reinterpret_cast<const Scene *>(scene), vec_norm, vec_north, offset_0, offset_1,
+                       nullptr, dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                       elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, stats, nullptr, hori_q, planes);
+}
+
 int hz_horizon_gridded_scene(const hz_scene *scene, const float *vec_norm, const float *vec_north,
                              int offset_0, int offset_1, float *hori_buffer, int dim_in_0, int dim_in_1,
                              int azim_num, float dist_search, float hori_acc, const char *ray_algorithm,
@@ -1231,7 +1289,8 @@ static int gridded_one_shot(const float *vert_grid, int dem_dim_0, int dem_dim_1
                             const char *ray_algorithm, const char *geom_type, const float *vert_simp,
                             int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
                             float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
-                            const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+                            const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats,
+                            uint16_t *hori_q = nullptr, int q_planes = 0) {
     Timer t; t.start();
     const bool verbose = opts && opts->verbose;
     if (verbose) {   // horizon_comp.cpp:643-645 (the engine named there is Embree)
@@ -1260,7 +1319,11 @@ static int gridded_one_shot(const float *vert_grid, int dem_dim_0, int dem_dim_1
         printf("BVH build time: %g s\n", local.t_bvh_s);
         printf("Total initialisation time: %g s\n", t.stop());
     }
-    if (hori_planes)
+    if (hori_q)
+        rc = hz_horizon_gridded_scene_q16(scene, vec_norm, vec_north, offset_0, offset_1, hori_q, q_planes, dim_in_0,
+                                          dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                                          elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
+    else if (hori_planes)
         rc = hz_horizon_gridded_scene_planes(scene, vec_norm, vec_north, offset_0, offset_1, hori_planes, dim_in_0,
                                              dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
                                              elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
@@ -1305,6 +1368,21 @@ int hz_horizon_gridded_planes(const float *vert_grid, int dem_dim_0, int dem_dim
                             dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm, geom_type, vert_simp,
                             num_vert_simp, tri_ind_simp, num_tri_simp, elev_ang_low_lim, mask, hori_fill, ray_org_elev,
                             opts, topo, stats);
+}
+
+int hz_horizon_gridded_q16(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
+                           const float *vec_north, int offset_0, int offset_1, uint16_t *hori_q, int planes,
+                           int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                           const char *ray_algorithm, const char *geom_type, const float *vert_simp,
+                           int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
+                           float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
+                           const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    const int rc = check_q16_call(hori_q, planes, dim_in_0, dim_in_1, azim_num, opts);
+    if (rc) return rc;
+    return gridded_one_shot(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north, offset_0, offset_1, nullptr, nullptr,
+                            dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm, geom_type, vert_simp,
+                            num_vert_simp, tri_ind_simp, num_tri_simp, elev_ang_low_lim, mask, hori_fill, ray_org_elev,
+                            opts, topo, stats, hori_q, planes);
 }
 
 int hz_horizon_locations_scene(const hz_scene *scene, const float *coords, const float *vec_norm,
@@ -1491,6 +1569,49 @@ int hz_hori_from_planes(const float *planes, int len_0, int len_1, int len_2, fl
     return planes_convert(false, planes, hori, len_0, len_1, len_2, device);
 }
 
+// ---------------------------------------------------------------------------------------
+// the 16-bit horizon code (hz_q16.hip; DESIGN.md section 4, clause 15)
+// ---------------------------------------------------------------------------------------
+// Elements per staging chunk of hz_hori_quantise / hz_hori_dequantise when a side is host memory: 64 Mi elements (256 MiB of
+// float32, 128 MiB of codes).  hz_debug_set("q16_chunk", n).
+static std::atomic<int> g_q16_chunk{0};
+
+// encode: src f32 -> dst u16, else src u16 -> dst f32; each side host or device memory, a host side goes through a chunk buffer
+static int q16_convert(bool encode, const void *src, size_t n, void *dst, int device) {
+    if (n == 0) return HZ_OK;
+    if (!src || !dst) return set_error(HZ_ERR_ARG, "NULL argument");
+    const size_t src_size = encode ? sizeof(float) : sizeof(uint16_t), dst_size = encode ? sizeof(uint16_t) : sizeof(float);
+    if ((reinterpret_cast<uintptr_t>(src) & (src_size - 1)) || (reinterpret_cast<uintptr_t>(dst) & (dst_size - 1)))
+        return set_error(HZ_ERR_ARG, "an array is not aligned to its element type");
+    if (n > (size_t)SIZE_MAX / sizeof(float)) return set_error(HZ_ERR_ARG, "the horizon is too large");
+    int rc = select_device(device);
+    if (rc) return rc;
+    hipStream_t st = nullptr;
+    const bool src_dev = is_device_ptr(src), dst_dev = is_device_ptr(dst);
+    const int knob = g_q16_chunk.load(std::memory_order_relaxed);
+    const size_t chunk = (src_dev && dst_dev) ? n : std::min(n, knob > 0 ? (size_t)knob : (size_t)64 << 20);
+    DevScratch d_src, d_dst;
+    if (!src_dev) HZ_HIP(hipMalloc(&d_src.p, chunk * src_size));
+    if (!dst_dev) HZ_HIP(hipMalloc(&d_dst.p, chunk * dst_size));
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        const char *in = static_cast<const char *>(src) + i0 * src_size;
+        char *out = static_cast<char *>(dst) + i0 * dst_size;
+        if (!src_dev) { HZ_HIP(hipMemcpyAsync(d_src.p, in, m * src_size, hipMemcpyHostToDevice, st)); in = static_cast<const char *>(d_src.p); }
+        void *o = dst_dev ? (void *)out : d_dst.p;
+        rc = encode ? hori_quantise_launch(reinterpret_cast<const float *>(in), m, static_cast<uint16_t *>(o), st)
+                    : hori_dequantise_launch(reinterpret_cast<const uint16_t *>(in), m, static_cast<float *>(o), st);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        if (!dst_dev) HZ_HIP(hipMemcpyAsync(out, o, m * dst_size, hipMemcpyDeviceToHost, st));
+        HZ_HIP(hipStreamSynchronize(st));           // the chunk buffers are used again
+    }
+    return HZ_OK;
+}
+
+int hz_hori_quantise(const float *src, size_t n, uint16_t *dst, int device) { return q16_convert(true, src, n, dst, device); }
+
+int hz_hori_dequantise(const uint16_t *src, size_t n, float *dst, int device) { return q16_convert(false, src, n, dst, device); }
+
 // hz_topo_params on planes: rows [rb, re) of every plane back into a bounded cell-major buffer (k_planes_to_hori), then the
 // reduction launch hz_topo_params makes on it -- no numerics are written again, so every map is the same words
 int hz_topo_params_planes(const float *azim, const float *planes, const float *vec_tilt, int len_0, int len_1, int len_2,
@@ -1598,6 +1719,7 @@ int hz_debug_set(const char *key, int value) {
     else if (!strcmp(key, "horisun_coarse_tile")) hz::g_horisun_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_coarse_route")) hz::g_horisun_coarse_route.store(value < 0 ? -1 : (value == 1 ? 1 : 0), std::memory_order_relaxed);
     else if (!strcmp(key, "planes_chunk")) g_planes_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "q16_chunk")) g_q16_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
 }
@@ -2192,6 +2314,7 @@ struct HorizonTerrain {
     const float *hori = nullptr;              // device; borrowed when the caller gave a device pointer
     bool own_hori = false;
     bool planes = false;                      // hori is f32[azim_num][cells] (hz_horizon_terrain_initialise_planes)
+    bool q16 = false;                         // hori addresses 16-bit codes in that layout (hz_horizon_terrain_initialise_q16)
     int azim_num = 0, dim_in_0 = 0, dim_in_1 = 0;
     void *vert = nullptr, *tilt = nullptr, *norm = nullptr, *north = nullptr, *enl = nullptr, *mask = nullptr;   // owned copies
     float fill = 0, ang_max = 89.0f;
@@ -2229,7 +2352,7 @@ int hz_horizon_terrain_create(int device, hz_horizon_terrain **terrain) {
     return HZ_OK;
 }
 
-static int horisun_initialise(hz_horizon_terrain *terrain, bool planes, const float *hori, int azim_num, const float *vert_grid,
+static int horisun_initialise(hz_horizon_terrain *terrain, bool planes, bool q16, const void *hori, int azim_num, const float *vert_grid,
                               int dem_dim_0, int dem_dim_1, int offset_0, int offset_1, const float *vec_tilt,
                               const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
                               const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
@@ -2252,10 +2375,10 @@ static int horisun_initialise(hz_horizon_terrain *terrain, bool planes, const fl
     Timer t_total; t_total.start();
     const size_t nc = plan.cells;
     int rc = HZ_OK;
-    if (is_device_ptr(hori)) { t->hori = hori; t->own_hori = false; }
+    if (is_device_ptr(hori)) { t->hori = static_cast<const float *>(hori); t->own_hori = false; }
     else {
         void *h = nullptr;
-        rc = horisun_copy(hori, nc * (size_t)azim_num * sizeof(float), st, &h);
+        rc = horisun_copy(hori, nc * (size_t)azim_num * (q16 ? sizeof(uint16_t) : sizeof(float)), st, &h);
         t->hori = static_cast<const float *>(h); t->own_hori = true;
     }
     if (!rc) rc = horisun_copy(vec_tilt, nc * 12, st, &t->tilt);
@@ -2279,7 +2402,7 @@ static int horisun_initialise(hz_horizon_terrain *terrain, bool planes, const fl
         if (e != hipSuccess) rc = set_error(HZ_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
     }
     if (rc) { horisun_release(t); return rc; }
-    t->azim_num = azim_num; t->dim_in_0 = dim_in_0; t->dim_in_1 = dim_in_1; t->planes = planes;
+    t->azim_num = azim_num; t->dim_in_0 = dim_in_0; t->dim_in_1 = dim_in_1; t->planes = planes; t->q16 = q16;
     t->fill = sw_dir_cor_fill; t->ang_max = ang_max;
     t->initialised = true;
     if (stats) {
@@ -2295,7 +2418,7 @@ int hz_horizon_terrain_initialise(hz_horizon_terrain *terrain, const float *hori
                                   const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
                                   const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
                                   hz_stats *stats) {
-    return horisun_initialise(terrain, false, hori, azim_num, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1, vec_tilt,
+    return horisun_initialise(terrain, false, false, hori, azim_num, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1, vec_tilt,
                               vec_norm, vec_north, dim_in_0, dim_in_1, surf_enl_fac, mask, sw_dir_cor_fill, ang_max, stats);
 }
 
@@ -2304,8 +2427,20 @@ int hz_horizon_terrain_initialise_planes(hz_horizon_terrain *terrain, const floa
                                          const float *vec_norm, const float *vec_north, int dim_in_0, int dim_in_1,
                                          const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill, float ang_max,
                                          hz_stats *stats) {
-    return horisun_initialise(terrain, true, planes, azim_num, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1, vec_tilt,
+    return horisun_initialise(terrain, true, false, planes, azim_num, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1, vec_tilt,
                               vec_norm, vec_north, dim_in_0, dim_in_1, surf_enl_fac, mask, sw_dir_cor_fill, ang_max, stats);
+}
+
+int hz_horizon_terrain_initialise_q16(hz_horizon_terrain *terrain, const uint16_t *hori_q, int azim_num, int planes,
+                                      const float *vert_grid, int dem_dim_0, int dem_dim_1, int offset_0, int offset_1,
+                                      const float *vec_tilt, const float *vec_norm, const float *vec_north, int dim_in_0,
+                                      int dim_in_1, const float *surf_enl_fac, const uint8_t *mask, float sw_dir_cor_fill,
+                                      float ang_max, hz_stats *stats) {
+    if (planes != 0 && planes != 1) return set_error(HZ_ERR_ARG, "planes must be 0 or 1");
+    if (reinterpret_cast<uintptr_t>(hori_q) & 1) return set_error(HZ_ERR_ARG, "hori_q is not aligned to 2 bytes");
+    return horisun_initialise(terrain, planes != 0, true, hori_q, azim_num, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                              vec_tilt, vec_norm, vec_north, dim_in_0, dim_in_1, surf_enl_fac, mask, sw_dir_cor_fill, ang_max,
+                              stats);
 }
 
 // Refraction on (elevation f32[cells], host or device: copied, as surf_enl_fac is) or off (NULL): the per-cell float64 factor of
@@ -2416,7 +2551,7 @@ int hz_horizon_terrain_run(hz_horizon_terrain *terrain, const float *sun_positio
             a.out_f32 = d_f32.dev ? d_f32.dev + nc * (size_t)s0 : nullptr;
             a.first = c == 0; a.last = c == plan.num_chunks - 1;
             // planes: the same launch plan, the horizon read as planes[k * cells + c] (k_horisun_planes, hz_planes.hip)
-            if ((rc = t->planes ? horisun_planes_launch(a, nc, plan.blocks, st) : horisun_launch(a, plan.blocks, st))) return rc;
+            if ((rc = t->planes ? horisun_planes_launch(a, nc, plan.blocks, st, t->q16) : horisun_launch(a, plan.blocks, st, t->q16))) return rc;
         }
         HZ_HIP(hipEventRecord(e1, st));
         HZ_HIP(hipEventSynchronize(e1));
@@ -2462,6 +2597,7 @@ int hz_horizon_terrain_sw_dir_cor_coarse(hz_horizon_terrain *terrain, const floa
     HorisunCoarsePlan cp;
     int rc;
     if ((rc = horisun_coarse_plan_for(t->dim_in_0, t->dim_in_1, p0, p1, k, t->planes, want_lit, want_sw, &cp))) return rc;
+    if (t->q16) cp.fallback = 1;      // codes: always the two-pass route, whatever "horisun_coarse_route" says (no fused kernel reads them)
     const size_t nc = plan.cells;
     const int gy = t->dim_in_0 / p0, gx = t->dim_in_1 / p1;
     const size_t ng = (size_t)gy * gx;
@@ -2512,7 +2648,7 @@ int hz_horizon_terrain_sw_dir_cor_coarse(hz_horizon_terrain *terrain, const floa
             a.num_sun = kc;
             float *o_sw = d_sw.dev ? d_sw.dev + ng * (size_t)s0 : nullptr, *o_lit = d_lit.dev ? d_lit.dev + ng * (size_t)s0 : nullptr;
             if (cp.fallback) {
-                if ((rc = t->planes ? horisun_planes_launch(a, nc, plan.blocks, st) : horisun_launch(a, plan.blocks, st))) return rc;
+                if ((rc = t->planes ? horisun_planes_launch(a, nc, plan.blocks, st, t->q16) : horisun_launch(a, plan.blocks, st, t->q16))) return rc;
                 if ((rc = coarse_reduce_launch(a.out_u8, a.out_f32, a.mask, n, t->dim_in_0, t->dim_in_1, p0, p1, kc, t->fill,
                                                o_sw, o_lit, st)))
                     return rc;
@@ -2621,7 +2757,7 @@ int hz_horizon_terrain_sun_times(hz_horizon_terrain *terrain, const float *sun_p
             a.t_before = s0 > 0 ? times_host[s0 - 1] : times_host[0];
             a.num_sun = kc;
             a.first = c == 0; a.last = c == plan.num_chunks - 1;
-            if ((rc = suntimes_launch(a, t->planes, plan.blocks, st))) return rc;
+            if ((rc = suntimes_launch(a, t->planes, plan.blocks, st, t->q16))) return rc;
         }
         HZ_HIP(hipEventRecord(e1, st));
         HZ_HIP(hipEventSynchronize(e1));

@@ -6,10 +6,12 @@
 // `accumulate`.  Per position: the float32 set-up of shadow_setup (hz_shadow.hip; written again here in the same order of
 // operations -- that file's machine code must not move), then, for the cells that pass the self-shading test, the sun's
 // azimuth and elevation in the cell's frame in float64 and two loads from the cell's horizon row.  A lane's row is 4 A bytes
-// from its neighbour's, so those two loads are uncoalesced; the per-position outputs out[s][cell] are coalesced.
+// from its neighbour's, so those two loads are uncoalesced; the per-position outputs out[s][cell] are coalesced.  The horizon's
+// element type is a template parameter: float, or the 16-bit codes of clause 15, decoded to float32 as they are loaded.
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
 #include "hz_horisun_refrac.h"
+#include "hz_q16.h"
 
 namespace hz {
 
@@ -22,8 +24,10 @@ __device__ __forceinline__ void horisun_unit(float &x, float &y, float &z) {
 }
 
 // terrain-shaded: the sun's elevation against the horizon row interpolated at the sun's azimuth, float64, every
-// product and sum rounded on its own (the library is built with -ffp-contract=off)
-__device__ __forceinline__ bool horisun_shaded(const float *__restrict__ row, int azim_num, double per_rad,
+// product and sum rounded on its own (the library is built with -ffp-contract=off).  H: float, or uint16_t for a row of
+// 16-bit codes, each decoded to float32 and widened (hori_value, hz_q16.h)
+template <typename H>
+__device__ __forceinline__ bool horisun_shaded(const H *__restrict__ row, int azim_num, double per_rad,
                                                float sx, float sy, float sz, float nx, float ny, float nz,
                                                float hx, float hy, float hz_, double ex, double ey, double ez) {
     const double cn = ((double)sx * (double)hx + (double)sy * (double)hy) + (double)sz * (double)hz_;
@@ -37,13 +41,14 @@ __device__ __forceinline__ bool horisun_shaded(const float *__restrict__ row, in
     const double t = u - kf;
     const int k = (int)kf;
     const int k0 = k % azim_num, k1 = (k + 1) % azim_num;
-    const double h = (1.0 - t) * (double)row[k0] + t * (double)row[k1];
+    const double h = (1.0 - t) * hori_value(row[k0]) + t * hori_value(row[k1]);
     const double alpha = asin(fmin(fmax(cu, -1.0), 1.0));
     return alpha < h;                                   // NaN horizon: false, the cell counts as lit
 }
 
 // REFRAC: the sun direction is bent by the atmospheric refraction first (clause 13; p.refrac_fac is not null)
-template <bool REFRAC>
+// H: the element type of p.hori (float; uint16_t: the codes of clause 15)
+template <bool REFRAC, typename H>
 __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun(HorisunArgs p) {
     const size_t c = (size_t)blockIdx.x * HZ_HORISUN_TPB + threadIdx.x;
     if (c >= p.cells) return;
@@ -73,7 +78,7 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun(HorisunArgs p) {
     const double ey = (double)north_z * (double)norm_x - (double)north_x * (double)norm_z;
     const double ez = (double)north_x * (double)norm_y - (double)north_y * (double)norm_x;
     const double per_rad = (double)p.azim_num / 6.283185307179586;
-    const float *row = p.hori + c * (size_t)p.azim_num;
+    const H *row = reinterpret_cast<const H *>(p.hori) + c * (size_t)p.azim_num;
     double a_sw = (p.sum_sw && !p.first) ? p.acc_sw[c] : 0.0;
     double a_lit = (p.sum_lit && !p.first) ? p.acc_lit[c] : 0.0;
     double fac = 0.0;
@@ -113,10 +118,16 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun(HorisunArgs p) {
     }
 }
 
-int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st) {
+int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st, bool q16) {
     if (a.cells == 0 || a.num_sun <= 0 || blocks == 0) return HZ_OK;
-    if (a.refrac_fac) hipLaunchKernelGGL(k_horisun<true>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, a);
-    else hipLaunchKernelGGL(k_horisun<false>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, a);
+    const dim3 grid(blocks), block(HZ_HORISUN_TPB);
+    if (q16) {
+        if (a.refrac_fac) hipLaunchKernelGGL((k_horisun<true, uint16_t>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_horisun<false, uint16_t>), grid, block, 0, st, a);
+    } else {
+        if (a.refrac_fac) hipLaunchKernelGGL((k_horisun<true, float>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_horisun<false, float>), grid, block, 0, st, a);
+    }
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }

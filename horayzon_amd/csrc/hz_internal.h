@@ -256,7 +256,7 @@ int coarse_reduce_launch(const uint8_t *codes, const float *vals, const uint8_t 
 // wanted): the lane's float64 sums start at 0 (first) or at acc_sw / acc_lit f64[cells], take w[s] * value in ascending s and
 // go back to acc_* or, in the last launch of a call, rounded once to sum_* (masked cells: fill)
 struct HorisunArgs {
-    const float *hori;                   // f32[cells][azim_num]
+    const float *hori;                   // f32[cells][azim_num]; the q16 launches read it as u16[cells][azim_num]
     const float *vert;                   // f32[cells][3]: the vertices of the inner domain
     const float *vec_tilt, *vec_norm, *vec_north, *surf_enl_fac;
     const uint8_t *mask;
@@ -271,7 +271,8 @@ struct HorisunArgs {
     int first, last;
     const double *refrac_fac;            // null: no refraction; else f64[cells], shadow_refrac_factor() (clause 13)
 };
-int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st);
+// q16: a.hori addresses 16-bit codes u16[cells][azim_num] (hz_q16.h, clause 15) instead of float32
+int horisun_launch(const HorisunArgs &a, unsigned blocks, hipStream_t st, bool q16 = false);
 
 // hz_planes.hip: the azimuth-major horizon layout planes[k][cell] (clause 11; device pointers).
 // Both transpositions move the `cells` x azim_num matrix `hori` (cell-major, contiguous) as 32-bit words; on the plane
@@ -282,7 +283,16 @@ int hori_to_planes_launch(const float *hori, size_t cells, int azim_num, float *
 int planes_to_hori_launch(const float *planes, size_t plane_stride, size_t cell0, size_t cells, int azim_num, float *hori,
                           hipStream_t st);
 // horisun_launch for a horizon stored as planes: a.hori = planes f32[azim_num][plane_stride] (k_horisun_planes)
-int horisun_planes_launch(const HorisunArgs &a, size_t plane_stride, unsigned blocks, hipStream_t st);
+// (q16: planes of 16-bit codes u16[azim_num][plane_stride])
+int horisun_planes_launch(const HorisunArgs &a, size_t plane_stride, unsigned blocks, hipStream_t st, bool q16 = false);
+
+// hz_q16.hip: the 16-bit horizon code (clause 15; device pointers).  dst[i] = encode(src[i]) /
+// decode(src[i]) for n elements; src and dst need the alignment of their element type only.  hori_quantise_planes_launch is
+// hori_to_planes_launch with encode applied on the way out: planes_q[k * plane_stride + cell0 + c] = encode(hori[c][k]).
+int hori_quantise_launch(const float *src, size_t n, uint16_t *dst, hipStream_t st);
+int hori_dequantise_launch(const uint16_t *src, size_t n, float *dst, hipStream_t st);
+int hori_quantise_planes_launch(const float *hori, size_t cells, int azim_num, uint16_t *planes_q, size_t plane_stride,
+                                size_t cell0, hipStream_t st);
 
 // hz_horisun_coarse.hip (hz_horizon_terrain_sw_dir_cor_coarse; device pointers): the plan of the fused kernel for chunks of
 // up to `chunk` positions (hz_horisun_coarse_plan.h; plan->fallback = 1: the shape, the "horisun_coarse_route" knob or the layout's default asks
@@ -302,7 +312,7 @@ int horisun_coarse_launch(const HorisunArgs &a, bool planes, size_t plane_stride
 // in the last launch of a call, to the maps sunrise / sunset / duration f32[cells] and intervals i32[cells] (null: not wanted;
 // masked cells: fill, -1).  A call of one launch (first and last) needs no state.  planes: hori = f32[azim_num][stride]
 struct SuntimesArgs {
-    const float *hori;                   // f32[cells][azim_num], or planes
+    const float *hori;                   // f32[cells][azim_num], or planes; the q16 launch reads 16-bit codes there
     size_t stride;                       // planes: words from one azimuth's plane to the next
     const float *vert;                   // f32[cells][3]: the vertices of the inner domain
     const float *vec_tilt, *vec_norm, *vec_north;
@@ -320,7 +330,8 @@ struct SuntimesArgs {
     float *sunrise, *sunset, *duration; int32_t *intervals;
 };
 size_t suntimes_state_bytes(size_t cells);
-int suntimes_launch(const SuntimesArgs &a, bool planes, unsigned blocks, hipStream_t st);
+// q16: a.hori addresses 16-bit codes (clause 15) in the layout `planes` names
+int suntimes_launch(const SuntimesArgs &a, bool planes, unsigned blocks, hipStream_t st, bool q16 = false);
 
 // hz_sort.hip: hand-written stable LSD radix sort (pairs) and exclusive scan, uint32
 size_t sort_temp_elems(size_t n);

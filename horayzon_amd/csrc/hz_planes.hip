@@ -12,10 +12,12 @@
 // k_horisun_planes is k_horisun (hz_horisun.hip) with row[k] read as planes[k * stride + c].  The sun's azimuth is
 // nearly the same in every cell's frame, so the lanes of a wave ask for the same one or two planes and their loads are
 // 64 consecutive words instead of 64 lines.  The arithmetic is written again here in the same order of operations
-// (that file's text does not move); both files are built with -ffp-contract=off, so the results are the same words.
+// (that file's text does not move); both files are built with -ffp-contract=off, so the results are the same words.  Like
+// k_horisun it takes the horizon's element type as a template parameter: float, or the 16-bit codes of clause 15 (hz_q16.h).
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
 #include "hz_horisun_refrac.h"
+#include "hz_q16.h"
 
 namespace hz {
 
@@ -122,7 +124,8 @@ __device__ __forceinline__ void planes_unit(float &x, float &y, float &z) {
 }
 
 // horisun_shaded of hz_horisun.hip: `col` = planes + c, the cell's horizon at azimuth k is col[k * stride]
-__device__ __forceinline__ bool planes_shaded(const float *__restrict__ col, size_t stride, int azim_num, double per_rad,
+template <typename H>
+__device__ __forceinline__ bool planes_shaded(const H *__restrict__ col, size_t stride, int azim_num, double per_rad,
                                               float sx, float sy, float sz, float nx, float ny, float nz,
                                               float hx, float hy, float hz_, double ex, double ey, double ez) {
     const double cn = ((double)sx * (double)hx + (double)sy * (double)hy) + (double)sz * (double)hz_;
@@ -136,13 +139,13 @@ __device__ __forceinline__ bool planes_shaded(const float *__restrict__ col, siz
     const double t = u - kf;
     const int k = (int)kf;
     const int k0 = k % azim_num, k1 = (k + 1) % azim_num;
-    const double h = (1.0 - t) * (double)col[(size_t)k0 * stride] + t * (double)col[(size_t)k1 * stride];
+    const double h = (1.0 - t) * hori_value(col[(size_t)k0 * stride]) + t * hori_value(col[(size_t)k1 * stride]);
     const double alpha = asin(fmin(fmax(cu, -1.0), 1.0));
     return alpha < h;                                   // NaN horizon: false, the cell counts as lit
 }
 
-// REFRAC: as k_horisun's
-template <bool REFRAC>
+// REFRAC, H: as k_horisun's
+template <bool REFRAC, typename H>
 __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun_planes(HorisunPlanesArgs q) {
     const HorisunArgs &p = q.a;
     const size_t c = (size_t)blockIdx.x * HZ_HORISUN_TPB + threadIdx.x;
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun_planes(HorisunPlanes
     const double ey = (double)north_z * (double)norm_x - (double)north_x * (double)norm_z;
     const double ez = (double)north_x * (double)norm_y - (double)north_y * (double)norm_x;
     const double per_rad = (double)p.azim_num / 6.283185307179586;
-    const float *col = p.hori + c;
+    const H *col = reinterpret_cast<const H *>(p.hori) + c;
     double a_sw = (p.sum_sw && !p.first) ? p.acc_sw[c] : 0.0;
     double a_lit = (p.sum_lit && !p.first) ? p.acc_lit[c] : 0.0;
     double fac = 0.0;
@@ -213,12 +216,18 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_horisun_planes(HorisunPlanes
     }
 }
 
-int horisun_planes_launch(const HorisunArgs &a, size_t plane_stride, unsigned blocks, hipStream_t st) {
+int horisun_planes_launch(const HorisunArgs &a, size_t plane_stride, unsigned blocks, hipStream_t st, bool q16) {
     if (a.cells == 0 || a.num_sun <= 0 || blocks == 0) return HZ_OK;
     HorisunPlanesArgs q;
     q.a = a; q.stride = plane_stride;
-    if (a.refrac_fac) hipLaunchKernelGGL(k_horisun_planes<true>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, q);
-    else hipLaunchKernelGGL(k_horisun_planes<false>, dim3(blocks), dim3(HZ_HORISUN_TPB), 0, st, q);
+    const dim3 grid(blocks), block(HZ_HORISUN_TPB);
+    if (q16) {
+        if (a.refrac_fac) hipLaunchKernelGGL((k_horisun_planes<true, uint16_t>), grid, block, 0, st, q);
+        else hipLaunchKernelGGL((k_horisun_planes<false, uint16_t>), grid, block, 0, st, q);
+    } else {
+        if (a.refrac_fac) hipLaunchKernelGGL((k_horisun_planes<true, float>), grid, block, 0, st, q);
+        else hipLaunchKernelGGL((k_horisun_planes<false, float>), grid, block, 0, st, q);
+    }
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }

@@ -15,6 +15,7 @@
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
 #include "hz_horisun_refrac.h"
+#include "hz_q16.h"
 
 namespace hz {
 
@@ -44,8 +45,10 @@ __device__ __forceinline__ void suntimes_refract(double fac, float norm_x, float
 }
 
 // horisun_shaded of hz_horisun.hip, returning alpha and h instead of their comparison.  `base` = the cell's first horizon
-// word, `step` = the distance of its azimuths in words (1: cell-major row, the plane stride: planes)
-__device__ __forceinline__ void suntimes_lookup(const float *__restrict__ base, size_t step, int azim_num, double per_rad,
+// word, `step` = the distance of its azimuths in words (1: cell-major row, the plane stride: planes).  H: float, or uint16_t
+// for the codes of clause 15 (hori_value, hz_q16.h)
+template <typename H>
+__device__ __forceinline__ void suntimes_lookup(const H *__restrict__ base, size_t step, int azim_num, double per_rad,
                                                 float sx, float sy, float sz, float nx, float ny, float nz,
                                                 float hx, float hy, float hz_, double ex, double ey, double ez,
                                                 double &alpha, double &h) {
@@ -60,12 +63,12 @@ __device__ __forceinline__ void suntimes_lookup(const float *__restrict__ base, 
     const double t = u - kf;
     const int k = (int)kf;
     const int k0 = k % azim_num, k1 = (k + 1) % azim_num;
-    h = (1.0 - t) * (double)base[(size_t)k0 * step] + t * (double)base[(size_t)k1 * step];
+    h = (1.0 - t) * hori_value(base[(size_t)k0 * step]) + t * hori_value(base[(size_t)k1 * step]);
     alpha = asin(fmin(fmax(cu, -1.0), 1.0));
 }
 
-// REFRAC: p.refrac_fac is not null (clause 13); PLANES: p.hori = planes f32[azim_num][p.stride]
-template <bool REFRAC, bool PLANES>
+// REFRAC: p.refrac_fac is not null (clause 13); PLANES: p.hori = planes [azim_num][p.stride]; H: the element type of p.hori
+template <bool REFRAC, bool PLANES, typename H>
 __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_suntimes(SuntimesArgs p) {
     const size_t c = (size_t)blockIdx.x * HZ_HORISUN_TPB + threadIdx.x;
     if (c >= p.cells) return;
@@ -91,7 +94,8 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_suntimes(SuntimesArgs p) {
     const double ey = (double)north_z * (double)norm_x - (double)north_x * (double)norm_z;
     const double ez = (double)north_x * (double)norm_y - (double)north_y * (double)norm_x;
     const double per_rad = (double)p.azim_num / 6.283185307179586;
-    const float *base = PLANES ? p.hori + c : p.hori + c * (size_t)p.azim_num;
+    const H *hori = reinterpret_cast<const H *>(p.hori);
+    const H *base = PLANES ? hori + c : hori + c * (size_t)p.azim_num;
     const size_t step = PLANES ? p.stride : 1;
     double fac = 0.0;
     if (REFRAC) fac = p.refrac_fac[c];
@@ -152,16 +156,22 @@ __global__ __launch_bounds__(HZ_HORISUN_TPB) void k_suntimes(SuntimesArgs p) {
 
 size_t suntimes_state_bytes(size_t cells) { return cells * (5 * sizeof(double) + sizeof(int32_t)); }
 
-int suntimes_launch(const SuntimesArgs &a, bool planes, unsigned blocks, hipStream_t st) {
+template <typename H>
+static void suntimes_launch_as(const SuntimesArgs &a, bool planes, dim3 grid, dim3 block, hipStream_t st) {
+    if (a.refrac_fac) {
+        if (planes) hipLaunchKernelGGL((k_suntimes<true, true, H>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_suntimes<true, false, H>), grid, block, 0, st, a);
+    } else {
+        if (planes) hipLaunchKernelGGL((k_suntimes<false, true, H>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_suntimes<false, false, H>), grid, block, 0, st, a);
+    }
+}
+
+int suntimes_launch(const SuntimesArgs &a, bool planes, unsigned blocks, hipStream_t st, bool q16) {
     if (a.cells == 0 || a.num_sun <= 0 || blocks == 0) return HZ_OK;
     const dim3 grid(blocks), block(HZ_HORISUN_TPB);
-    if (a.refrac_fac) {
-        if (planes) hipLaunchKernelGGL((k_suntimes<true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_suntimes<true, false>), grid, block, 0, st, a);
-    } else {
-        if (planes) hipLaunchKernelGGL((k_suntimes<false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_suntimes<false, false>), grid, block, 0, st, a);
-    }
+    if (q16) suntimes_launch_as<uint16_t>(a, planes, grid, block, st);
+    else suntimes_launch_as<float>(a, planes, grid, block, st);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
 }

@@ -15,6 +15,11 @@ from ._lib import Scene, hz_opts, hz_stats, hz_topo_out, ptr
 
 TOPO_NAMES = ("svf", "vsf", "openness")     # the reductions `topo=` can ask for (hz_opts.svf, hz_topo_out.vsf / .openness)
 LAYOUTS = ("cell_major", "azim_major")      # hori (y, x, azim) as the reference has it, or planes (azim, y, x)
+HORI_DTYPES = ("float32", "uint16")         # the horizon as float32 [radian] or as the 16-bit code of `quantise`
+# the 16-bit horizon code (clause 15): 65535 levels over [-pi/2, pi/2] and one code for NaN
+Q16_NAN = 0xFFFF
+Q16_STEP = 1.5707963267948966 / 32767.0     # [radian] between two codes
+Q16_MAX_ERROR = Q16_STEP / 2 + 2 ** -24     # of decode(encode(v)) for v in range: half a step and half a float32 ulp below 2 rad
 last_stats = None   # hz_stats of the most recent call as a dict (timers, ray count)
 # test hook: defaults of the launch-schedule options ("left_min", "persist_grid", "left_cap_test": hz_opts) for calls that do not
 # pass them -- lets the parity tests run their cases under other schedules without touching every call
@@ -84,6 +89,56 @@ def to_cell_major(planes, *, device=0):
     return _convert(planes, False, device)
 
 
+def _q16_tensor_dtype():
+    import torch
+    return getattr(torch, "uint16", torch.int16)      # (older torch: int16 carries the same bits)
+
+
+def _q16_convert(a, encode, device):
+    name = "hori" if encode else "q"
+    tensor = not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+    if not isinstance(a, np.ndarray) and not tensor:
+        raise TypeError("Argument '%s' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
+                        % (name, type(a).__name__))
+    dtype = str(a.dtype).split(".")[-1]
+    accepted = ("float32",) if encode else (("uint16", "int16") if tensor else ("uint16",))
+    if dtype not in accepted:
+        raise ValueError("Buffer dtype mismatch, expected '%s_t' but got '%s'" % (accepted[0], dtype))
+    if not (a.is_contiguous() if tensor else a.flags["C_CONTIGUOUS"]):
+        raise ValueError("array '%s' is not C-contiguous" % name)
+    shape = tuple(a.shape)
+    if tensor:
+        import torch
+        if a.device.type != "cuda":
+            raise ValueError("tensor '%s' is not on a GPU" % name)
+        device = a.device.index
+        out = torch.empty(shape, dtype=_q16_tensor_dtype() if encode else torch.float32, device=a.device)
+        torch.cuda.synchronize(a.device)          # the library works on a stream of its own
+        n = a.numel()
+    else:
+        out = np.empty(shape, dtype=np.uint16 if encode else np.float32)
+        n = a.size
+    L = _lib.lib()
+    _lib.check((L.hz_hori_quantise if encode else L.hz_hori_dequantise)(ptr(a), n, ptr(out), device))
+    return out
+
+
+def quantise(hori, *, device=0):
+    """``hori`` float32 [radian], any shape -> the 16-bit horizon code, uint16 of the same shape, encoded on the GPU
+    (clause 15): ``rint`` of the angle, clamped to [-pi/2, pi/2], in steps of ``Q16_STEP`` = 0.0027
+    degrees, plus 32767; NaN becomes ``Q16_NAN``.  ``dequantise(quantise(v))`` is within ``Q16_MAX_ERROR`` of every ``v`` in
+    range.  A NumPy array gives a NumPy array (staged through the GPU ``device`` in bounded chunks); a torch tensor on a GPU
+    gives a torch tensor on that GPU (``torch.uint16``, or ``torch.int16`` with the same bits where torch has no uint16).
+    The input must be C-contiguous.  The code is elementwise: it is the same for both horizon layouts."""
+    return _q16_convert(hori, True, device)
+
+
+def dequantise(q, *, device=0):
+    """The decoder of ``quantise``: codes uint16 (for a tensor also int16 carrying the same bits), any shape -> float32
+    [radian]; ``Q16_NAN`` gives NaN.  ``quantise(dequantise(q)) == q`` for every code."""
+    return _q16_convert(q, False, device)
+
+
 def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     offset_0, offset_1, dist_search, azim_num=360, hori_acc=0.25,
                     ray_algorithm="guess_constant", geom_type="grid",
@@ -93,7 +148,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     num_tri_simp=1, elev_ang_low_lim=-15.0, mask=None,
                     hori_fill=0.0, ray_org_elev=0.01, *, device=0, verbose=False,
                     scene=None, svf_vec_tilt=None, svf_only=False, rows=None, count_work=False, devices=None,
-                    topo=None, topo_vec_tilt=None, topo_only=False, layout="cell_major",
+                    topo=None, topo_vec_tilt=None, topo_only=False, layout="cell_major", hori_dtype="float32",
                     _top_nodes=-1, _regroup=-1, _hit_cache=True, _chunk_rows=0, _near_skip=True, _level_stack=False,
                     _verify_near=False, _left_min=0, _persist_grid=0, _verbose=0):
     """Horizon computation for gridded domain.
@@ -123,7 +178,11 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     (y, x, azim_num); "azim_major": the returned horizon is float32 (azim_num, y, x), the planes
     ``to_azim_major`` makes of the cell-major result, word for word -- the layout ``HorizonTerrain`` reads
     fastest; the cell-major array is never materialised, every other argument keeps its meaning, and
-    ``svf_only`` / ``topo_only`` are refused: there is nothing to lay out).
+    ``svf_only`` / ``topo_only`` are refused: there is nothing to lay out), ``hori_dtype`` ("float32"; "uint16": the returned
+    horizon is ``quantise`` of the float32 horizon of the same ``layout``, word for word, at half the bytes in memory and
+    over the bus -- each chunk of rows is encoded on the GPU after it was traced and reduced, so the maps of ``topo`` /
+    ``svf_vec_tilt`` are those of the float32 call; with ``rows`` the rest of the array is ``Q16_NAN``; ``svf_only`` /
+    ``topo_only`` are refused).
     """
     global last_stats
     _check_f32(vert_grid, 1, "vert_grid")
@@ -180,6 +239,11 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     planes = check_layout(layout)
     if planes and (svf_only or topo_only):
         raise ValueError("'svf_only' / 'topo_only' cannot be combined with layout=\"azim_major\": there is no horizon to lay out")
+    if not isinstance(hori_dtype, str) or hori_dtype not in HORI_DTYPES:
+        raise ValueError("unknown 'hori_dtype': %r (choose from %r)" % (hori_dtype, HORI_DTYPES))
+    q16 = hori_dtype == "uint16"
+    if q16 and (svf_only or topo_only):
+        raise ValueError("'svf_only' / 'topo_only' cannot be combined with hori_dtype=\"uint16\": there is no horizon to encode")
 
     # Ensure that passed arrays are contiguous in memory (horizon.pyx:159-163)
     vert_grid = np.ascontiguousarray(vert_grid)
@@ -194,9 +258,9 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     if svf_only and svf_vec_tilt is None:
         raise ValueError("'svf_only' needs 'svf_vec_tilt'")
     hori_shape = (azim_num, dim_in_0, dim_in_1) if planes else (dim_in_0, dim_in_1, azim_num)
-    hori_buffer = None if (svf_only or topo_only) else np.empty(hori_shape, dtype=np.float32)
+    hori_buffer = None if (svf_only or topo_only) else np.empty(hori_shape, dtype=np.uint16 if q16 else np.float32)
     if rows is not None and hori_buffer is not None:
-        hori_buffer.fill(np.nan)   # only a slab is written; every cell is written otherwise
+        hori_buffer.fill(Q16_NAN if q16 else np.nan)   # only a slab is written; every cell is written otherwise
                                    # (masked ones get hori_fill), so the 18 GB pre-fill is skipped
 
     opts = hz_opts()
@@ -252,20 +316,23 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     def run(o, st):
         # (the _ex entry points only when hz_topo_out has a map: every other call reaches the library as before)
         ex = () if topo_out is None else (C.byref(topo_out),)
-        if planes:                                # (the planes forms always take the `topo` argument)
+        if planes or q16:                         # (the planes and q16 forms always take the `topo` argument)
             ex = ex or (None,)
+        lay = (int(planes),) if q16 else ()       # (the q16 forms: `int planes` after hori_q)
         if scene is None:
-            return (L.hz_horizon_gridded_planes if planes else L.hz_horizon_gridded_ex if ex else L.hz_horizon_gridded)(
+            return (L.hz_horizon_gridded_q16 if q16 else L.hz_horizon_gridded_planes if planes
+                    else L.hz_horizon_gridded_ex if ex else L.hz_horizon_gridded)(
                 ptr(vert_grid), dem_dim_0, dem_dim_1, ptr(vec_norm), ptr(vec_north),
-                offset_0, offset_1, ptr(hori_buffer), dim_in_0, dim_in_1, azim_num,
+                offset_0, offset_1, ptr(hori_buffer), *lay, dim_in_0, dim_in_1, azim_num,
                 dist_search, hori_acc, ray_algorithm.encode("utf-8"),
                 geom_type.encode("utf-8"), ptr(vert_simp), num_vert_simp,
                 ptr(tri_ind_simp), num_tri_simp, elev_ang_low_lim, ptr(mask),
                 hori_fill, ray_org_elev, C.byref(o), *ex, C.byref(st))
         o.device = scene.device
-        return (L.hz_horizon_gridded_scene_planes if planes else L.hz_horizon_gridded_scene_ex if ex else L.hz_horizon_gridded_scene)(
+        return (L.hz_horizon_gridded_scene_q16 if q16 else L.hz_horizon_gridded_scene_planes if planes
+                else L.hz_horizon_gridded_scene_ex if ex else L.hz_horizon_gridded_scene)(
             scene._h, ptr(vec_norm), ptr(vec_north), offset_0, offset_1,
-            ptr(hori_buffer), dim_in_0, dim_in_1, azim_num, dist_search, hori_acc,
+            ptr(hori_buffer), *lay, dim_in_0, dim_in_1, azim_num, dist_search, hori_acc,
             ray_algorithm.encode("utf-8"), elev_ang_low_lim, ptr(mask), hori_fill,
             ray_org_elev, C.byref(o), *ex, C.byref(st))
 

@@ -373,10 +373,39 @@ class HorizonTerrain:
         self._initialise(True, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
                          vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max)
 
+    def initialise_q16(self, azim, hori_q, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                       vec_tilt, vec_norm, vec_north, surf_enl_fac, mask,
+                       sw_dir_cor_fill=np.nan, ang_max=89.0, *, layout="cell_major"):
+        """``initialise`` with the horizon as 16-bit codes (clause 15): ``hori_q`` uint16 (y, x,
+        azim_num), or (azim_num, y, x) with ``layout="azim_major"`` -- what ``horizon_gridded(hori_dtype="uint16")`` returns
+        or ``horizon.quantise`` makes of a float32 horizon (NumPy: copied; torch tensor on the object's GPU, ``torch.uint16``
+        or ``torch.int16`` with the same bits: borrowed).  Half the bytes of the float32 horizon in HBM.  Every method then
+        gives, word for word, what it gives on the float32 horizon ``horizon.dequantise(hori_q)`` in the same layout;
+        ``sw_dir_cor_coarse`` always takes the two-pass route.  Every other argument and check is ``initialise``'s.  (A method
+        of its own: ``initialise`` and ``initialise_azim_major`` keep taking float32 only.)"""
+        from .horizon import check_layout
+        self._initialise(check_layout(layout), azim, hori_q, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
+                         vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max, q16=True)
+
+    def _typed_hori_q(self, hori_q):
+        """``_typed_hori`` for codes: uint16, for a tensor also int16."""
+        if isinstance(hori_q, np.ndarray):
+            _typed(hori_q, np.uint16, 3, "hori_q")
+            return
+        if not hasattr(hori_q, "data_ptr"):
+            raise TypeError("Argument 'hori_q' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
+                            % type(hori_q).__name__)
+        if hori_q.dim() != 3:
+            raise ValueError("Buffer has wrong number of dimensions (expected 3, got %d)" % hori_q.dim())
+        if str(hori_q.dtype).split(".")[-1] not in ("uint16", "int16"):
+            raise ValueError("Buffer dtype mismatch, expected 'uint16' but got '%s'" % hori_q.dtype)
+        if hori_q.device.type != "cuda" or hori_q.device.index != self.device:
+            raise ValueError("tensor 'hori_q' is not on the HorizonTerrain's device (cuda:%d)" % self.device)
+
     def _initialise(self, planes, azim, hori, vert_grid, dem_dim_0, dem_dim_1, offset_0, offset_1,
-                    vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max):
+                    vec_tilt, vec_norm, vec_north, surf_enl_fac, mask, sw_dir_cor_fill, ang_max, q16=False):
         _typed(azim, np.float32, 1, "azim")
-        self._typed_hori(hori)
+        (self._typed_hori_q if q16 else self._typed_hori)(hori)
         _typed(vert_grid, np.float32, 1, "vert_grid")
         _typed(vec_tilt, np.float32, 3, "vec_tilt")
         _typed(vec_norm, np.float32, 3, "vec_norm")
@@ -396,7 +425,7 @@ class HorizonTerrain:
              lambda: not V.same_leading_shape(vectors, 3, 3) or vec_tilt.shape[2] != 3),
             (ValueError, "Inconsistent/incorrect shape of 'surf_enl_fac' and/or 'mask'",
              lambda: not V.same_leading_shape((vec_tilt[..., 0], surf_enl_fac, mask), 2, 2)),
-            (ValueError, "Inconsistent/incorrect shape of 'hori'",
+            (ValueError, "Inconsistent/incorrect shape of '%s'" % ("hori_q" if q16 else "hori"),
              lambda: cells != vec_tilt.shape[:2] or num < 1),
             (ValueError, "'azim' is not the azimuth array of horizon_gridded",
              lambda: azim.shape[0] != num or not np.array_equal(azim, gridded_azimuths(num))),
@@ -412,8 +441,10 @@ class HorizonTerrain:
         self._shape = None
         self._refrac = False                                 # the library drops the factor with the old arrays
         L = _lib.lib()
-        _lib.check((L.hz_horizon_terrain_initialise_planes if planes else L.hz_horizon_terrain_initialise)(
-            self._h, ptr(hori), num, ptr(vert_grid), dem_dim_0, dem_dim_1, offset_0, offset_1,
+        entry = L.hz_horizon_terrain_initialise_q16 if q16 else \
+            (L.hz_horizon_terrain_initialise_planes if planes else L.hz_horizon_terrain_initialise)
+        _lib.check(entry(
+            self._h, ptr(hori), num, *((int(planes),) if q16 else ()), ptr(vert_grid), dem_dim_0, dem_dim_1, offset_0, offset_1,
             ptr(vec_tilt), ptr(vec_norm), ptr(vec_north), vec_tilt.shape[0], vec_tilt.shape[1],
             ptr(surf_enl_fac), ptr(mask), sw_dir_cor_fill, ang_max, C.byref(st)))
         self._hori = hori if _is_tensor(hori) else None      # keep a borrowed horizon alive
@@ -425,8 +456,8 @@ class HorizonTerrain:
         f32 (y, x) [m]: the orthometric elevation of the inner-domain cells, ``Terrain.initialise``'s ``elevation`` (a
         C-contiguous NumPy array, copied; no range check, as there); ``None`` switches it off.  With it, ``shadow``,
         ``sw_dir_cor``, the batch forms, ``accumulate`` and ``sw_dir_cor_coarse`` answer for the sun as the atmosphere bends
-        it over each cell -- ``Terrain``'s ``refrac_cor=True`` -- on both horizon layouts.  ``initialise`` and
-        ``initialise_azim_major`` switch it off again."""
+        it over each cell -- ``Terrain``'s ``refrac_cor=True`` -- on both horizon layouts.  ``initialise``,
+        ``initialise_azim_major`` and ``initialise_q16`` switch it off again."""
         if elevation is not None:
             _typed(elevation, np.float32, 2, "elevation")
         if self._shape is None:

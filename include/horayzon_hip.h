@@ -285,6 +285,51 @@ int hz_hori_from_planes(const float *planes, int len_0, int len_1, int len_2, fl
 int hz_topo_params_planes(const float *azim, const float *planes, const float *vec_tilt, int len_0, int len_1, int len_2,
                           float *svf, float *vsf, float *openness, int device);
 
+/* ------------------------------------------------------------------------- */
+/* The 16-bit horizon code (additive; DESIGN.md section 4, clause 15): half the bytes of the float32 horizon.     */
+/* All arithmetic is float64, every operation rounded on its own, rint rounds half to even:                      */
+/*   HALF_PI = 1.5707963267948966, SCALE = 32767.0 / HALF_PI, STEP = HALF_PI / 32767.0                           */
+/*   encode(v): NaN -> 0xFFFF; else (uint16)(rint(fmin(fmax((double)v, -HALF_PI), HALF_PI) * SCALE) + 32767.0)    */
+/*   decode(q): 0xFFFF -> the quiet NaN 0x7FC00000; else (float)((double)((int)q - 32767) * STEP)                */
+/* +-0 encodes to 32767 and decodes to +0.0f; +-inf and finite values outside [-pi/2, pi/2] (a hori_fill, say)    */
+/* clamp to the ends; encode(decode(q)) == q for every q; |decode(encode(v)) - v| <= STEP / 2 + 2^-24 rad in      */
+/* range.  The code is elementwise: planes_q[k][y][x] and hori_q[y][x][k] hold the same 16-bit word.              */
+/* ------------------------------------------------------------------------- */
+/* dst[i] = encode(src[i]) / decode(src[i]), i < n.  Either side may be host or device memory, in any mix, aligned */
+/* to its element type (a view at an odd element is fine); a host side is staged in bounded chunks                */
+/* ("q16_chunk" elements).  n == 0 succeeds.                                                                      */
+int hz_hori_quantise(const float *src, size_t n, uint16_t *dst, int device);
+int hz_hori_dequantise(const uint16_t *src, size_t n, float *dst, int device);
+/* hz_horizon_gridded_planes / _scene_planes with `hori_q` in place of hori_planes (host or device memory):       */
+/* planes = 0: u16[rows][dim_in_1][azim_num], planes = 1: u16[azim_num][rows][dim_in_1].  Each chunk of rows is    */
+/* traced into the bounded float32 chunk buffer, reduced there -- opts->svf and topo come from the unquantised     */
+/* chunk and are bit-identical to the float call's maps -- and then encoded (planes = 1: and transposed) into its  */
+/* place: hori_q == encode(what the float call of the same layout writes), word for word.  A device hori_q is      */
+/* written in place; a host hori_q goes through one more chunk buffer of half the size and one copy.  Row slabs,   */
+/* hori_is_slab, inputs_are_slab and chunk_rows mean what they mean for hori_planes; rows outside the slab are     */
+/* left untouched.  opts->skip_hori is HZ_ERR_ARG.  stats->scratch_bytes includes the chunk buffers; t_d2h_s       */
+/* includes the chunk copies of a host hori_q.                                                                     */
+int hz_horizon_gridded_q16(const float *vert_grid, int dem_dim_0, int dem_dim_1,
+                           const float *vec_norm, const float *vec_north,
+                           int offset_0, int offset_1,
+                           uint16_t *hori_q, int planes, int dim_in_0, int dim_in_1,
+                           int azim_num, float dist_search, float hori_acc,
+                           const char *ray_algorithm, const char *geom_type,
+                           const float *vert_simp, int num_vert_simp,
+                           const int32_t *tri_ind_simp, int num_tri_simp,
+                           float elev_ang_low_lim, const uint8_t *mask,
+                           float hori_fill, float ray_org_elev,
+                           const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+int hz_horizon_gridded_scene_q16(const hz_scene *scene,
+                                 const float *vec_norm, const float *vec_north,
+                                 int offset_0, int offset_1,
+                                 uint16_t *hori_q, int planes, int dim_in_0, int dim_in_1,
+                                 int azim_num, float dist_search, float hori_acc,
+                                 const char *ray_algorithm,
+                                 float elev_ang_low_lim, const uint8_t *mask,
+                                 float hori_fill, float ray_org_elev,
+                                 const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+
 /* Horizon (and optionally distance to the horizon) for arbitrary locations; argument list     */
 /* mirrors horizon_locations_comp (horizon_comp.h:22-34, horizon_comp.cpp:828-1094).           */
 /* coords f32[num_loc][3], vec_norm / vec_north f32[num_loc][3], ray_org_elev f32[num_loc],    */
@@ -352,6 +397,7 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* tile take the kernel without LDS), "horisun_chunk" = sun positions per launch of hz_horizon_terrain_run (<= 0: the default), */
 /* "horisun_coarse_route" / "horisun_coarse_tile": see hz_horizon_terrain_sw_dir_cor_coarse (< 0: the default),                 */
 /* "planes_chunk" = cells per staging chunk of hz_hori_to_planes / _from_planes / hz_topo_params_planes (<= 0: the default),   */
+/* "q16_chunk" = elements per staging chunk of hz_hori_quantise / hz_hori_dequantise (<= 0: the default),                        */
 /* "leaf_lend" = 0: the horizon kernel's fast stack runs without leaf lending (1 or < 0: the default, with it)                  */
 /* "flat_refill" = 0: guess_constant's refill runs the search state machine's if-chain (1 or < 0: the default, the branch-free */
 /* pass; it belongs to the instantiations with leaf lending, so "leaf_lend" = 0 switches it off too)                            */
@@ -503,6 +549,17 @@ int hz_horizon_terrain_initialise(hz_horizon_terrain* t, const float* hori, int 
 /* copied; device: borrowed).  hz_horizon_terrain_run then reads hori[k mod A] as planes[k mod A][cell]; the     */
 /* arithmetic, the chunking of positions, the sums and the outputs are the same, and so is every result.         */
 int hz_horizon_terrain_initialise_planes(hz_horizon_terrain* t, const float* planes, int azim_num,
+        const float* vert_grid, int dem_dim_0, int dem_dim_1, int offset_0, int offset_1,
+        const float* vec_tilt, const float* vec_norm, const float* vec_north, int dim_in_0, int dim_in_1,
+        const float* surf_enl_fac, const uint8_t* mask, float sw_dir_cor_fill, float ang_max, hz_stats* stats);
+/* hz_horizon_terrain_initialise with the horizon given as 16-bit codes (clause 15): hori_q u16[dim_in_0][dim_in_1][azim_num]    */
+/* (planes = 0) or u16[azim_num][dim_in_0][dim_in_1] (planes = 1); host: copied, device: borrowed.  Refraction is off afterwards. */
+/* hz_horizon_terrain_run, _sun_times, _sw_dir_cor_coarse and _refraction then work on the handle unchanged: every kernel loads  */
+/* the two codes, applies decode as written above (float64 product, rounded to float32), widens that float32 to float64 and       */
+/* continues with clause 10, 13 or 14, so every output is, word for word, that of a handle initialised with the float32 array     */
+/* decode(hori_q) of the same layout.  hz_horizon_terrain_sw_dir_cor_coarse always takes the two-pass route on such a handle:     */
+/* hz_debug_set("horisun_coarse_route", 0) is ignored for it (the fused kernel has no form that reads codes).                    */
+int hz_horizon_terrain_initialise_q16(hz_horizon_terrain* t, const uint16_t* hori_q, int azim_num, int planes,
         const float* vert_grid, int dem_dim_0, int dem_dim_1, int offset_0, int offset_1,
         const float* vec_tilt, const float* vec_norm, const float* vec_north, int dim_in_0, int dim_in_1,
         const float* surf_enl_fac, const uint8_t* mask, float sw_dir_cor_fill, float ang_max, hz_stats* stats);
