@@ -89,7 +89,7 @@ def test_input_preparation_chain(hip, ellps):
     T, D = hip.transform, hip.direction
     X, Y, Z = T.lonlat2ecef(d[k + "lon"], d[k + "lat"], d[k + "h"], ellps=ellps)
     for got, ref in ((X, d[k + "X"]), (Y, d[k + "Y"]), (Z, d[k + "Z"])):
-        assert np.abs(got - ref).max() <= 1e-8 * 6.4e6            # float64, ~1e-15 relative
+        assert np.abs(got - ref).max() <= 1e-8                    # metres: float64, ~1.6e-15 relative (10 ulp at 6.4e6 m)
     org = d[k + "origin"]
     tr = T.TransformerEcef2enu(lon_or=org[0], lat_or=org[1], ellps=ellps)
     assert np.allclose([tr.x_ecef_or, tr.y_ecef_or, tr.z_ecef_or], org[2:], rtol=1e-15, atol=1e-8)
