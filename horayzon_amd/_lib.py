@@ -101,7 +101,10 @@ SYMBOLS = (
     "hz_horizon_terrain_sw_dir_cor_coarse", "hz_horizon_terrain_refraction", "hz_horizon_terrain_sun_times",
     "hz_hori_quantise", "hz_hori_dequantise", "hz_horizon_gridded_q16", "hz_horizon_gridded_scene_q16",
     "hz_horizon_terrain_initialise_q16",
+    "hz_horizon_distance", "hz_horizon_distance_scene", "hz_horizon_gridded_dist", "hz_horizon_gridded_scene_dist",
 )
+# hori_kind of the horizon-distance calls: the layout and the element type of `hori`, or'ed
+HORI_PLANES, HORI_U16 = 1, 2
 
 
 def _preload_hip_runtime():
@@ -165,6 +168,16 @@ def lib():
                                          + L.hz_horizon_gridded_ex.argtypes[8:])
     L.hz_horizon_gridded_scene_q16.argtypes = (L.hz_horizon_gridded_scene_ex.argtypes[:6] + [ip]
                                                + L.hz_horizon_gridded_scene_ex.argtypes[6:])
+    # the _dist forms: `hori`, `int hori_kind` and `dist_buffer` in place of hori_buffer
+    L.hz_horizon_gridded_dist.argtypes = (L.hz_horizon_gridded_ex.argtypes[:8] + [ip, vp]
+                                          + L.hz_horizon_gridded_ex.argtypes[8:])
+    L.hz_horizon_gridded_scene_dist.argtypes = (L.hz_horizon_gridded_scene_ex.argtypes[:6] + [ip, vp]
+                                                + L.hz_horizon_gridded_scene_ex.argtypes[6:])
+    L.hz_horizon_distance.argtypes = [vp, ip, ip, vp, ip, vp, vp, vp, ip, ip, ip, ip, ip, C.c_float, C.c_float,
+                                      C.c_char_p, vp, ip, vp, ip, C.c_float, vp, C.c_float,
+                                      C.POINTER(hz_opts), C.POINTER(hz_stats)]
+    L.hz_horizon_distance_scene.argtypes = [vp, vp, ip, vp, vp, vp, ip, ip, ip, ip, ip, C.c_float, C.c_float,
+                                            C.c_float, vp, C.c_float, C.POINTER(hz_opts), C.POINTER(hz_stats)]
     L.hz_hori_quantise.argtypes = [vp, C.c_size_t, vp, ip]
     L.hz_hori_dequantise.argtypes = [vp, C.c_size_t, vp, ip]
     L.hz_hori_to_planes.argtypes = [vp, ip, ip, ip, vp, ip]

@@ -550,7 +550,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
                        float dist_search, float hori_acc, const char *ray_algorithm,
                        float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
                        const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats, float *hori_planes = nullptr,
-                       uint16_t *hori_q = nullptr, int q_planes = 0) {
+                       uint16_t *hori_q = nullptr, int q_planes = 0, float *dist_buffer = nullptr, int dist_planes = 0) {
     int alg = 2;
     int rc = parse_alg(ray_algorithm, &alg);
     if (rc) return rc;
@@ -570,6 +570,10 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     if (to_layout && skip_hori)
         return set_error(HZ_ERR_ARG, "skip_hori with %s: there is nothing to lay out", to_q16 ? "hori_q" : "hori_planes");
     if (to_layout) hori_buffer = nullptr;
+    // dist_buffer (hz_horizon_gridded_dist): the distance to the horizon (hz_horidist.hip) of every chunk, from the float32 chunk
+    // on the device; cell-major, or (dist_planes) planes like hori_planes
+    const bool want_dist = dist_buffer != nullptr;
+    if (want_dist && skip_hori) return set_error(HZ_ERR_ARG, "skip_hori with dist_buffer: there is no horizon to return it with");
     if (!hori_buffer && !skip_hori && !to_layout) return set_error(HZ_ERR_ARG, "hori_buffer is NULL");
     if (opts && opts->svf && !opts->vec_tilt) return set_error(HZ_ERR_ARG, "opts.svf needs opts.vec_tilt");
     // the SVF weights sectors by azim[1] - azim[0] (topo_param.pyx:433): undefined for a single azimuth
@@ -676,6 +680,22 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     } else {
         if ((rc = d_hori.bind(hori_slab_host, slab_cells * (size_t)azim_num))) return rc;
     }
+    // the distances of a chunk: cell-major in a chunk buffer unless dist_buffer is device memory in that layout; planes reach
+    // a device dist_buffer through the transposition of hori_planes, a host one through one more chunk buffer
+    const bool dist_on_dev = want_dist && is_device_ptr(dist_buffer);
+    void *tmp_dist = nullptr, *tmp_dist_planes = nullptr;
+    TmpFree tmp_free5{&tmp_dist}, tmp_free6{&tmp_dist_planes};
+    if (want_dist && (!dist_on_dev || dist_planes)) {
+        HZ_HIP(hipMalloc(&tmp_dist, (size_t)chunk_rows * row_bytes)); tmp_bytes += (size_t)chunk_rows * row_bytes;
+        if (dist_planes && !dist_on_dev) { HZ_HIP(hipMalloc(&tmp_dist_planes, (size_t)chunk_rows * row_bytes)); tmp_bytes += (size_t)chunk_rows * row_bytes; }
+    }
+    unsigned long long *dist_cnt = nullptr;      // [0] distance rays, [1] cells
+    struct CntFree { unsigned long long **p; ~CntFree() { if (*p) (void)hipFree(*p); } } dist_cnt_free{&dist_cnt};
+    if (want_dist) {
+        HZ_HIP(hipMalloc((void **)&dist_cnt, 2 * sizeof(unsigned long long)));
+        HZ_HIP(hipMemsetAsync(dist_cnt, 0, 2 * sizeof(unsigned long long), st));
+    }
+    float ms_dist = 0.0f, ms_dist_copy = 0.0f;
     std::vector<float> azim_h;
     if (want_topo) {   // azim as the wrapper recomputes it, horizon.pyx:191-195
         azim_h.resize((size_t)azim_num);
@@ -730,7 +750,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     unsigned long long redo_blocks = 0, redo_groups = 0;
 
     // HIP events on the kernels' stream: horizon kernel and SVF kernel are timed separately
-    struct Ev { hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr, l = nullptr, q = nullptr, r = nullptr; };
+    struct Ev { hipEvent_t a = nullptr, b = nullptr, c = nullptr, d = nullptr, l = nullptr, q = nullptr, r = nullptr, s = nullptr, t = nullptr; };
     std::vector<Ev> evs;          // one per launch attempt
     std::vector<size_t> ev_of;    // chunk -> its final attempt
     hipStream_t st_copy = nullptr;
@@ -743,6 +763,8 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
             if (e.l) (void)hipEventDestroy(e.l);
             if (e.q) (void)hipEventDestroy(e.q);
             if (e.r) (void)hipEventDestroy(e.r);
+            if (e.s) (void)hipEventDestroy(e.s);
+            if (e.t) (void)hipEventDestroy(e.t);
         }
         if (st_copy) { stream_release(sc->device, st_copy); st_copy = nullptr; }
     };
@@ -923,6 +945,40 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
                                            want_open ? d_open.dev + o : nullptr, st);
             }
             (void)hipEventRecord(e.c, st);
+            if (!rc && want_dist) {
+                // the distances of this chunk from its float32 horizon, before that is laid out or encoded (the kernel time is
+                // e.c .. e.s, the copy to a host dist_buffer e.s .. e.t)
+                const size_t cc = (size_t)(re - rb) * dim_in_1, c0 = plane_cell0 + (size_t)(rb - row_begin) * dim_in_1;
+                const size_t A = (size_t)azim_num;
+                float *dist_chunk = tmp_dist ? (float *)tmp_dist : dist_buffer + c0 * A;
+                HoridistArgs da;
+                da.vec_norm = norm0; da.vec_north = north0; da.mask = mask0;
+                da.hori = hori_chunk; da.dist = dist_chunk; da.q16 = 0; da.planes = 0;
+                da.hori_stride = da.hori_cell0 = da.dist_stride = da.dist_cell0 = 0;
+                da.offset_0 = offset_0; da.offset_1 = offset_1; da.dim_in_1 = dim_in_1; da.row_begin = rb; da.row_end = re;
+                da.azim_num = azim_num; da.elev_num = tb.elev_num;
+                da.hori_acc = tb.hori_acc; da.up = tb.up; da.dist_m = dist_m; da.ray_org_elev = ray_org_elev;
+                da.azim_sin = d_as.dev; da.azim_cos = d_ac.dev; da.elev_ang = d_ea.dev; da.elev_sin = d_es.dev; da.elev_cos = d_ec.dev;
+                da.block_w = 8; da.counters = dist_cnt;
+                Ev &ed = evs.back();
+                if (hipEventCreate(&ed.s) != hipSuccess || hipEventCreate(&ed.t) != hipSuccess)
+                    return fail(set_error(HZ_ERR_HIP, "hipEventCreate failed"));
+                rc = horidist_launch(sc, da, st);
+                (void)hipEventRecord(ed.s, st);
+                if (!rc && dist_planes) {
+                    if (dist_on_dev) rc = hori_to_planes_launch(dist_chunk, cc, azim_num, dist_buffer, plane_stride, c0, st);
+                    else {
+                        rc = hori_to_planes_launch(dist_chunk, cc, azim_num, (float *)tmp_dist_planes, cc, 0, st);
+                        if (!rc && hipMemcpy2DAsync(dist_buffer + c0, plane_stride * sizeof(float), tmp_dist_planes, cc * sizeof(float),
+                                                    cc * sizeof(float), A, hipMemcpyDeviceToHost, st) != hipSuccess)
+                            rc = set_error(HZ_ERR_HIP, "copy of the distance planes failed: %s", hipGetErrorString(hipGetLastError()));
+                    }
+                } else if (!rc && !dist_on_dev) {
+                    if (hipMemcpyAsync(dist_buffer + c0 * A, dist_chunk, cc * A * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess)
+                        rc = set_error(HZ_ERR_HIP, "copy of the distances failed: %s", hipGetErrorString(hipGetLastError()));
+                }
+                (void)hipEventRecord(ed.t, st);
+            }
             if (!rc && to_planes) {
                 // the chunk into its rows of every plane: in place for device planes, through the chunk-planes buffer and one
                 // strided copy (azim_num rows of the chunk's cells, pitch = plane stride) for host planes
@@ -969,6 +1025,11 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
             ms += m1; ms_svf += m2;
             if (evs.back().l) { float m3 = 0.0f; (void)hipEventElapsedTime(&m3, evs.back().l, e.b); ms_left += m3; }
             if (evs.back().r) { float m4 = 0.0f; (void)hipEventElapsedTime(&m4, evs.back().q, evs.back().r); ms_q_copy += m4; }
+            if (evs.back().t) {
+                float m5 = 0.0f, m6 = 0.0f;
+                (void)hipEventElapsedTime(&m5, e.c, evs.back().s); (void)hipEventElapsedTime(&m6, evs.back().s, evs.back().t);
+                ms_dist += m5; ms_dist_copy += m6;
+            }
             for (int k = 0; k < 16; k++) cnt[k] += c[k];
             left_cells += c[28]; left_again += c[29];
             n_verified += c[21];
@@ -997,8 +1058,13 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     if ((rc = d_open.finish(st))) return rc;
     HZ_HIP(hipStreamSynchronize(st));
     const double d2h_s = t_d2h.stop();
+    unsigned long long dcnt[2] = {0, 0};
+    if (want_dist) HZ_HIP(hipMemcpy(dcnt, dist_cnt, sizeof(dcnt), hipMemcpyDeviceToHost));
 
     if (stats) {
+        // (a call with dist_buffer: the distance rays and their kernel count as rays and ray tracing time, the copies of a
+        //  host dist_buffer -- inside the loop, after the chunk's kernel -- as device-to-host time)
+        stats->num_rays += dcnt[0]; stats->t_kernel_s += (double)ms_dist * 1e-3; stats->t_d2h_s += (double)ms_dist_copy * 1e-3;
         stats->num_rays += cnt[0]; stats->guard_events += cnt[1];
         stats->nodes_visited += cnt[2]; stats->tris_tested += cnt[3]; stats->num_cells += cnt[4];
         stats->wave_node_iters += cnt[5]; stats->wave_leaf_iters += cnt[6]; stats->wave_refills += cnt[7];
@@ -1111,6 +1177,137 @@ static int locations_run(const Scene *sc, const float *coords, const float *vec_
         printf("Number of locations for which horizon is computed: %d \n", num_loc);
         printf("Ray tracing time: %g s\n", (double)ms * 1e-3);
         printf("Number of rays shot: %llu\n", cnt[0]);
+    }
+    return HZ_OK;
+}
+
+// The distance to the horizon of a stored horizon (hz_horidist.hip; DESIGN.md section 4, clause 16).  hori_kind: bit 0 = planes,
+// bit 1 = 16-bit codes.  `hori` and `dist` address inner-domain row 0 (or, opts.hori_is_slab, row_begin) in the layout of the
+// kind.  Two device arrays are one launch; a host side moves chunk by chunk through a bounded device buffer (opts.chunk_rows
+// rows, else about 1 GiB of horizon and distances together), copy in -- kernel -- copy out on the scene's stream.
+static int horidist_run(const Scene *sc, const void *hori, int hori_kind, float *dist, const float *vec_norm,
+                        const float *vec_north, int offset_0, int offset_1, int dim_in_0, int dim_in_1, int azim_num,
+                        float dist_search, float hori_acc, float elev_ang_low_lim, const uint8_t *mask, float ray_org_elev,
+                        const hz_opts *opts, hz_stats *stats) {
+    int rc = HZ_OK;
+    if (hori_kind < 0 || hori_kind > 3) return set_error(HZ_ERR_ARG, "hori_kind must be 0 ... 3 (bit 0: planes, bit 1: 16-bit codes)");
+    const bool planes = (hori_kind & HZ_HORI_PLANES) != 0, q16 = (hori_kind & HZ_HORI_U16) != 0;
+    const size_t es = q16 ? sizeof(uint16_t) : sizeof(float);
+    if (!hori || !dist) return set_error(HZ_ERR_ARG, "hori and dist must not be NULL");
+    if ((reinterpret_cast<uintptr_t>(hori) & (es - 1)) || (reinterpret_cast<uintptr_t>(dist) & 3))
+        return set_error(HZ_ERR_ARG, "hori or dist is not aligned to its element type");
+    if (!vec_norm || !vec_north || !mask) return set_error(HZ_ERR_ARG, "vec_norm, vec_north and mask must not be NULL");
+    if (dim_in_0 <= 0 || dim_in_1 <= 0 || azim_num <= 0) return set_error(HZ_ERR_ARG, "dim_in_0, dim_in_1 and azim_num must be positive");
+    if (offset_0 < 0 || offset_1 < 0 || offset_0 + dim_in_0 > sc->hdr.d0 || offset_1 + dim_in_1 > sc->hdr.d1)
+        return set_error(HZ_ERR_ARG, "inconsistency between input arguments dem_dim_0, dem_dim_1, offset_0, offset_1 and vec_norm");
+    if (!(hori_acc > 0.0f) || hori_acc > 10.0f) return set_error(HZ_ERR_ARG, "limit of hori_acc (10 degree) is exceeded");
+    int row_begin = 0, row_end = dim_in_0;      // the row slab: as in horizon_run
+    if (opts && !(opts->row_begin == 0 && opts->row_end == 0)) {
+        row_begin = opts->row_begin;
+        row_end = (opts->row_end == -1) ? dim_in_0 : opts->row_end;
+        if (row_begin < 0 || row_end < 0 || row_end > dim_in_0 || row_begin > row_end)
+            return set_error(HZ_ERR_ARG, "invalid row slab [%d, %d) for dim_in_0 = %d", opts->row_begin, opts->row_end, dim_in_0);
+        if (row_begin == row_end) return HZ_OK;
+    }
+    HZ_HIP(hipSetDevice(sc->device));
+    std::lock_guard<std::mutex> run_lock(sc->run_mu);
+    hipStream_t st = sc->stream;
+    Timer t_total; t_total.start();
+    HostTables tb;
+    build_tables(azim_num, hori_acc, elev_ang_low_lim, tb);
+    if (tb.elev_num < 2) return set_error(HZ_ERR_ARG, "elevation table is empty (elev_ang_low_lim too high)");
+    const float dist_m = (float)((double)dist_search * 1000.0);
+
+    const size_t A = (size_t)azim_num;
+    const size_t ncell = (size_t)dim_in_0 * dim_in_1, slab_cells = (size_t)(row_end - row_begin) * dim_in_1;
+    Timer t_h2d; t_h2d.start();
+    DevIn<float> d_norm, d_north, d_as, d_ac, d_ea, d_es, d_ec;
+    DevIn<uint8_t> d_mask;
+    const bool inputs_are_slab = opts && opts->inputs_are_slab;
+    const size_t in_off = (size_t)row_begin * dim_in_1, src_off = inputs_are_slab ? 0 : in_off;
+    if ((rc = d_norm.bind(vec_norm + 3 * src_off, slab_cells * 3, st))) return rc;
+    if ((rc = d_north.bind(vec_north + 3 * src_off, slab_cells * 3, st))) return rc;
+    if ((rc = d_mask.bind(mask + src_off, slab_cells, st))) return rc;
+    if ((rc = d_as.bind(tb.azim_sin.data(), A, st))) return rc;
+    if ((rc = d_ac.bind(tb.azim_cos.data(), A, st))) return rc;
+    if ((rc = d_ea.bind(tb.elev_ang.data(), (size_t)tb.elev_num, st))) return rc;
+    if ((rc = d_es.bind(tb.elev_sin.data(), (size_t)tb.elev_num, st))) return rc;
+    if ((rc = d_ec.bind(tb.elev_cos.data(), (size_t)tb.elev_num, st))) return rc;
+    DevIn<unsigned long long> d_cnt;
+    HZ_HIP(hipMalloc(&d_cnt.owned, 2 * sizeof(unsigned long long)));
+    HZ_HIP(hipMemsetAsync(d_cnt.owned, 0, 2 * sizeof(unsigned long long), st));
+    const bool hori_is_slab = opts && opts->hori_is_slab;
+    const size_t plane_stride = hori_is_slab ? slab_cells : ncell;
+    const size_t cell_base = hori_is_slab ? 0 : in_off;      // the slab's first cell in hori / dist
+    const bool h_dev = is_device_ptr(hori), d_dev = is_device_ptr(dist);
+    const size_t row_in = (size_t)dim_in_1 * A * es, row_out = (size_t)dim_in_1 * A * sizeof(float);
+    int chunk_rows = row_end - row_begin;
+    if (!(h_dev && d_dev)) {
+        if (opts && opts->chunk_rows > 0) chunk_rows = std::min(chunk_rows, opts->chunk_rows);
+        else chunk_rows = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk_rows, ((size_t)1 << 30) / (row_in + row_out)));
+    }
+    void *tmp_in = nullptr, *tmp_out = nullptr;
+    struct TmpFree { void **p; ~TmpFree() { if (*p) (void)hipFree(*p); } } tmp_free{&tmp_in}, tmp_free2{&tmp_out};
+    size_t tmp_bytes = 0;
+    if (!h_dev) { HZ_HIP(hipMalloc(&tmp_in, (size_t)chunk_rows * row_in)); tmp_bytes += (size_t)chunk_rows * row_in; }
+    if (!d_dev) { HZ_HIP(hipMalloc(&tmp_out, (size_t)chunk_rows * row_out)); tmp_bytes += (size_t)chunk_rows * row_out; }
+    HZ_HIP(hipStreamSynchronize(st));
+    double h2d_s = t_h2d.stop();
+
+    HoridistArgs a;
+    a.vec_norm = d_norm.dev - 3 * in_off; a.vec_north = d_north.dev - 3 * in_off; a.mask = d_mask.dev - in_off;
+    a.q16 = q16 ? 1 : 0; a.planes = planes ? 1 : 0;
+    a.offset_0 = offset_0; a.offset_1 = offset_1; a.dim_in_1 = dim_in_1;
+    a.azim_num = azim_num; a.elev_num = tb.elev_num;
+    a.hori_acc = tb.hori_acc; a.up = tb.up; a.dist_m = dist_m; a.ray_org_elev = ray_org_elev;
+    a.azim_sin = d_as.dev; a.azim_cos = d_ac.dev; a.elev_ang = d_ea.dev; a.elev_sin = d_es.dev; a.elev_cos = d_ec.dev;
+    a.block_w = g_horidist_block_w.load(std::memory_order_relaxed);
+    a.counters = static_cast<unsigned long long *>(d_cnt.owned);
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct EvFree { hipEvent_t *e; ~EvFree() { for (int k = 0; k < 4; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_free{ev};
+    for (int k = 0; k < 4; k++) HZ_HIP(hipEventCreate(&ev[k]));
+    float ms_in = 0.0f, ms_kernel = 0.0f, ms_out = 0.0f;
+    const char *hori_b = static_cast<const char *>(hori);
+    for (int rb = row_begin; rb < row_end; rb += chunk_rows) {
+        const int re = std::min(rb + chunk_rows, row_end);
+        const size_t cc = (size_t)(re - rb) * dim_in_1, c0 = cell_base + (size_t)(rb - row_begin) * dim_in_1;
+        a.row_begin = rb; a.row_end = re;
+        HZ_HIP(hipEventRecord(ev[0], st));
+        if (h_dev) {
+            a.hori = planes ? hori : static_cast<const void *>(hori_b + c0 * A * es);
+            a.hori_stride = plane_stride; a.hori_cell0 = c0;
+        } else {
+            if (planes) HZ_HIP(hipMemcpy2DAsync(tmp_in, cc * es, hori_b + c0 * es, plane_stride * es, cc * es, A, hipMemcpyHostToDevice, st));
+            else HZ_HIP(hipMemcpyAsync(tmp_in, hori_b + c0 * A * es, cc * A * es, hipMemcpyHostToDevice, st));
+            a.hori = tmp_in; a.hori_stride = cc; a.hori_cell0 = 0;
+        }
+        if (d_dev) { a.dist = planes ? dist : dist + c0 * A; a.dist_stride = plane_stride; a.dist_cell0 = c0; }
+        else { a.dist = static_cast<float *>(tmp_out); a.dist_stride = cc; a.dist_cell0 = 0; }
+        HZ_HIP(hipEventRecord(ev[1], st));
+        if ((rc = horidist_launch(sc, a, st))) { (void)hipStreamSynchronize(st); return rc; }
+        HZ_HIP(hipEventRecord(ev[2], st));
+        if (!d_dev) {
+            if (planes) HZ_HIP(hipMemcpy2DAsync(dist + c0, plane_stride * sizeof(float), tmp_out, cc * sizeof(float), cc * sizeof(float), A,
+                                                hipMemcpyDeviceToHost, st));
+            else HZ_HIP(hipMemcpyAsync(dist + c0 * A, tmp_out, cc * A * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        HZ_HIP(hipEventRecord(ev[3], st));
+        if (hipStreamSynchronize(st) != hipSuccess)
+            return set_error(HZ_ERR_HIP, "horizon distance kernel failed: %s", hipGetErrorString(hipGetLastError()));
+        float m = 0.0f;
+        (void)hipEventElapsedTime(&m, ev[0], ev[1]); ms_in += m;
+        (void)hipEventElapsedTime(&m, ev[1], ev[2]); ms_kernel += m;
+        (void)hipEventElapsedTime(&m, ev[2], ev[3]); ms_out += m;
+    }
+    unsigned long long cnt[2] = {0, 0};
+    HZ_HIP(hipMemcpy(cnt, d_cnt.owned, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (stats) {
+        stats->num_rays += cnt[0]; stats->num_cells += cnt[1];
+        stats->t_kernel_s += (double)ms_kernel * 1e-3;
+        stats->t_h2d_s += h2d_s + (double)ms_in * 1e-3; stats->t_d2h_s += (double)ms_out * 1e-3;
+        stats->t_total_s += t_total.stop();
+        stats->elev_num = tb.elev_num; stats->bvh_height = sc->hdr.height; stats->scene_bytes = sc->hdr.total_bytes;
+        stats->scratch_bytes = (uint64_t)tmp_bytes;
     }
     return HZ_OK;
 }
@@ -1290,7 +1487,8 @@ static int gridded_one_shot(const float *vert_grid, int dem_dim_0, int dem_dim_1
                             int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
                             float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
                             const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats,
-                            uint16_t *hori_q = nullptr, int q_planes = 0) {
+                            uint16_t *hori_q = nullptr, int q_planes = 0, void *hori_any = nullptr, int hori_kind = 0,
+                            float *dist_buffer = nullptr) {
     Timer t; t.start();
     const bool verbose = opts && opts->verbose;
     if (verbose) {   // horizon_comp.cpp:643-645 (the engine named there is Embree)
@@ -1319,7 +1517,11 @@ static int gridded_one_shot(const float *vert_grid, int dem_dim_0, int dem_dim_1
         printf("BVH build time: %g s\n", local.t_bvh_s);
         printf("Total initialisation time: %g s\n", t.stop());
     }
-    if (hori_q)
+    if (dist_buffer)
+        rc = hz_horizon_gridded_scene_dist(scene, vec_norm, vec_north, offset_0, offset_1, hori_any, hori_kind, dist_buffer,
+                                           dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
+                                           elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
+    else if (hori_q)
         rc = hz_horizon_gridded_scene_q16(scene, vec_norm, vec_north, offset_0, offset_1, hori_q, q_planes, dim_in_0,
                                           dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm,
                                           elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, &local);
@@ -1383,6 +1585,82 @@ int hz_horizon_gridded_q16(const float *vert_grid, int dem_dim_0, int dem_dim_1,
                             dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm, geom_type, vert_simp,
                             num_vert_simp, tri_ind_simp, num_tri_simp, elev_ang_low_lim, mask, hori_fill, ray_org_elev,
                             opts, topo, stats, hori_q, planes);
+}
+
+// `hori` of hori_kind (bit 0: planes, bit 1: 16-bit codes) plus the distances: the checks that need no device
+static int check_dist_call(const void *hori, int hori_kind, const float *dist_buffer, int dim_in_0, int dim_in_1, int azim_num,
+                           const hz_opts *opts) {
+    if (hori_kind < 0 || hori_kind > 3) return set_error(HZ_ERR_ARG, "hori_kind must be 0 ... 3 (bit 0: planes, bit 1: 16-bit codes)");
+    if (!hori) return set_error(HZ_ERR_ARG, "hori is NULL");
+    if (!dist_buffer) return set_error(HZ_ERR_ARG, "dist_buffer is NULL");
+    if ((hori_kind & HZ_HORI_U16) && (reinterpret_cast<uintptr_t>(hori) & 1)) return set_error(HZ_ERR_ARG, "hori is not aligned to 2 bytes");
+    if (dim_in_0 <= 0 || dim_in_1 <= 0 || azim_num <= 0) return set_error(HZ_ERR_ARG, "dim_in_0, dim_in_1 and azim_num must be positive");
+    if (opts && opts->skip_hori) return set_error(HZ_ERR_ARG, "skip_hori with dist_buffer: there is no horizon to return it with");
+    return HZ_OK;
+}
+
+int hz_horizon_gridded_scene_dist(const hz_scene *scene, const float *vec_norm, const float *vec_north,
+                                  int offset_0, int offset_1, void *hori, int hori_kind, float *dist_buffer,
+                                  int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                                  const char *ray_algorithm, float elev_ang_low_lim, const uint8_t *mask, float hori_fill,
+                                  float ray_org_elev, const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    if (!scene) return set_error(HZ_ERR_ARG, "scene is NULL");
+    const int rc = check_dist_call(hori, hori_kind, dist_buffer, dim_in_0, dim_in_1, azim_num, opts);
+    if (rc) return rc;
+    const int planes = hori_kind & HZ_HORI_PLANES;
+    const bool q16 = (hori_kind & HZ_HORI_U16) != 0;
+    return horizon_run(reinterpret_cast<const Scene *>(scene), vec_norm, vec_north, offset_0, offset_1,
+                       (!q16 && !planes) ? static_cast<float *>(hori) : nullptr, dim_in_0, dim_in_1, azim_num, dist_search,
+                       hori_acc, ray_algorithm, elev_ang_low_lim, mask, hori_fill, ray_org_elev, opts, topo, stats,
+                       (!q16 && planes) ? static_cast<float *>(hori) : nullptr, q16 ? static_cast<uint16_t *>(hori) : nullptr,
+                       planes, dist_buffer, planes);
+}
+
+int hz_horizon_gridded_dist(const float *vert_grid, int dem_dim_0, int dem_dim_1, const float *vec_norm,
+                            const float *vec_north, int offset_0, int offset_1, void *hori, int hori_kind,
+                            float *dist_buffer, int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                            const char *ray_algorithm, const char *geom_type, const float *vert_simp,
+                            int num_vert_simp, const int32_t *tri_ind_simp, int num_tri_simp,
+                            float elev_ang_low_lim, const uint8_t *mask, float hori_fill, float ray_org_elev,
+                            const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats) {
+    const int rc = check_dist_call(hori, hori_kind, dist_buffer, dim_in_0, dim_in_1, azim_num, opts);
+    if (rc) return rc;
+    return gridded_one_shot(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north, offset_0, offset_1, nullptr, nullptr,
+                            dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, ray_algorithm, geom_type, vert_simp,
+                            num_vert_simp, tri_ind_simp, num_tri_simp, elev_ang_low_lim, mask, hori_fill, ray_org_elev,
+                            opts, topo, stats, nullptr, 0, hori, hori_kind, dist_buffer);
+}
+
+int hz_horizon_distance_scene(const hz_scene *scene, const void *hori, int hori_kind, float *dist,
+                              const float *vec_norm, const float *vec_north, int offset_0, int offset_1,
+                              int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                              float elev_ang_low_lim, const uint8_t *mask, float ray_org_elev,
+                              const hz_opts *opts, hz_stats *stats) {
+    if (!scene) return set_error(HZ_ERR_ARG, "scene is NULL");
+    return horidist_run(reinterpret_cast<const Scene *>(scene), hori, hori_kind, dist, vec_norm, vec_north, offset_0, offset_1,
+                        dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, elev_ang_low_lim, mask, ray_org_elev, opts, stats);
+}
+
+int hz_horizon_distance(const float *vert_grid, int dem_dim_0, int dem_dim_1, const void *hori, int hori_kind, float *dist,
+                        const float *vec_norm, const float *vec_north, int offset_0, int offset_1,
+                        int dim_in_0, int dim_in_1, int azim_num, float dist_search, float hori_acc,
+                        const char *geom_type, const float *vert_simp, int num_vert_simp,
+                        const int32_t *tri_ind_simp, int num_tri_simp, float elev_ang_low_lim, const uint8_t *mask,
+                        float ray_org_elev, const hz_opts *opts, hz_stats *stats) {
+    Timer t; t.start();
+    if (!hori || !dist) return set_error(HZ_ERR_ARG, "hori and dist must not be NULL");
+    hz_scene *scene = nullptr;
+    hz_stats local;
+    memset(&local, 0, sizeof(local));
+    int rc = hz_scene_create(vert_grid, dem_dim_0, dem_dim_1, geom_type, vert_simp, num_vert_simp,
+                             tri_ind_simp, num_tri_simp, opts ? opts->device : 0, &scene, &local);
+    if (rc) return rc;
+    rc = hz_horizon_distance_scene(scene, hori, hori_kind, dist, vec_norm, vec_north, offset_0, offset_1, dim_in_0, dim_in_1,
+                                   azim_num, dist_search, hori_acc, elev_ang_low_lim, mask, ray_org_elev, opts, &local);
+    hz_scene_destroy(scene);
+    local.t_total_s = t.stop();
+    if (stats) *stats = local;
+    return rc;
 }
 
 int hz_horizon_locations_scene(const hz_scene *scene, const float *coords, const float *vec_norm,
@@ -1720,6 +1998,15 @@ int hz_debug_set(const char *key, int value) {
     else if (!strcmp(key, "horisun_coarse_route")) hz::g_horisun_coarse_route.store(value < 0 ? -1 : (value == 1 ? 1 : 0), std::memory_order_relaxed);
     else if (!strcmp(key, "planes_chunk")) g_planes_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "q16_chunk")) g_q16_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "horidist_traversal")) {    // (< 0: the default; results never depend on it)
+        if (value > 1) return hz::set_error(HZ_ERR_ARG, "hz_debug_set: horidist_traversal is 0 or 1");
+        hz::g_horidist_traversal.store(value, std::memory_order_relaxed);
+    }
+    else if (!strcmp(key, "horidist_block_w")) {      // (< 0: the default, 8; results never depend on it)
+        if (value >= 0 && value != 8 && value != 16 && value != 32 && value != 64)
+            return hz::set_error(HZ_ERR_ARG, "hz_debug_set: horidist_block_w is 8, 16, 32 or 64");
+        hz::g_horidist_block_w.store(value < 0 ? 8 : value, std::memory_order_relaxed);
+    }
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
 }

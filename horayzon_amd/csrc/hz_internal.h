@@ -294,6 +294,31 @@ int hori_dequantise_launch(const uint16_t *src, size_t n, float *dst, hipStream_
 int hori_quantise_planes_launch(const float *hori, size_t cells, int azim_num, uint16_t *planes_q, size_t plane_stride,
                                 size_t cell0, hipStream_t st);
 
+// hz_horidist.hip: the distance to the horizon of a gridded horizon (clause 16; device pointers).  One
+// launch over the rows [row_begin, row_end) of the inner domain.  vec_norm, vec_north and mask are indexed by the cell of the
+// inner domain, the scene's vertices by offset_0 / offset_1.  Cell c (0 = the first cell of row_begin) and azimuth k of the
+// horizon is element c * azim_num + k of `hori`, or (planes) element k * hori_stride + hori_cell0 + c; `dist` likewise with
+// its own stride and first cell.  q16: `hori` holds 16-bit codes (hz_q16.h) instead of float32.  block_w: cells of a wave's
+// block in a row (8: the 8 x 8 block of k_horizon; 16, 32, 64: flatter blocks).  counters: device u64[2], [0] += distance
+// rays, [1] += cells with mask == 1.
+struct HoridistArgs {
+    const float *vec_norm, *vec_north;
+    const uint8_t *mask;
+    const void *hori;
+    float *dist;
+    int q16, planes;
+    size_t hori_stride, hori_cell0, dist_stride, dist_cell0;
+    int offset_0, offset_1, dim_in_1, row_begin, row_end;
+    int azim_num, elev_num;
+    float hori_acc, up, dist_m, ray_org_elev;      // radians / metres
+    const float *azim_sin, *azim_cos, *elev_ang, *elev_sin, *elev_cos;   // device tables
+    int block_w;
+    unsigned long long *counters;
+};
+int horidist_launch(const Scene *sc, const HoridistArgs &a, hipStream_t st);
+extern std::atomic<int> g_horidist_traversal;   // "horidist_traversal" (hz_debug_set): 0 hz_closest's slot order, 1 (default, also < 0) the children of a node front to back
+extern std::atomic<int> g_horidist_block_w;  // "horidist_block_w" (hz_debug_set): cells per row of a wave's block in the planes launches (default 8)
+
 // hz_horisun_coarse.hip (hz_horizon_terrain_sw_dir_cor_coarse; device pointers): the plan of the fused kernel for chunks of
 // up to `chunk` positions (hz_horisun_coarse_plan.h; plan->fallback = 1: the shape, the "horisun_coarse_route" knob or the layout's default asks
 // for the two-pass route), and one launch of k_horisun_coarse over the a.num_sun <= chunk positions of a chunk: block means

@@ -139,6 +139,10 @@ def dequantise(q, *, device=0):
     return _q16_convert(q, False, device)
 
 
+def _hori_kind(planes, q16):
+    return (_lib.HORI_PLANES if planes else 0) | (_lib.HORI_U16 if q16 else 0)
+
+
 def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     offset_0, offset_1, dist_search, azim_num=360, hori_acc=0.25,
                     ray_algorithm="guess_constant", geom_type="grid",
@@ -149,7 +153,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                     hori_fill=0.0, ray_org_elev=0.01, *, device=0, verbose=False,
                     scene=None, svf_vec_tilt=None, svf_only=False, rows=None, count_work=False, devices=None,
                     topo=None, topo_vec_tilt=None, topo_only=False, layout="cell_major", hori_dtype="float32",
-                    _top_nodes=-1, _regroup=-1, _hit_cache=True, _chunk_rows=0, _near_skip=True, _level_stack=False,
+                    hori_dist=False, _top_nodes=-1, _regroup=-1, _hit_cache=True, _chunk_rows=0, _near_skip=True, _level_stack=False,
                     _verify_near=False, _left_min=0, _persist_grid=0, _verbose=0):
     """Horizon computation for gridded domain.
 
@@ -182,6 +186,11 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     horizon is ``quantise`` of the float32 horizon of the same ``layout``, word for word, at half the bytes in memory and
     over the bus -- each chunk of rows is encoded on the GPU after it was traced and reduced, so the maps of ``topo`` /
     ``svf_vec_tilt`` are those of the float32 call; with ``rows`` the rest of the array is ``Q16_NAN``; ``svf_only`` /
+    ``topo_only`` are refused), ``hori_dist`` (True: the distance to the horizon [metre] is computed in the same call and
+    returned as second value -- ``(hori, dist, azim)``, the order of ``horizon_locations``, or ``(hori, dist, azim, third)``
+    where a third value is returned -- float32 in ``layout``; it is ``horizon_distance`` of the float32 horizon of this call,
+    word for word, also with ``hori_dtype="uint16"``: each chunk of rows gets its distances on the GPU before it is laid out
+    or encoded; the horizon and the maps are those of the call without it; with ``rows`` the rest is NaN; ``svf_only`` /
     ``topo_only`` are refused).
     """
     global last_stats
@@ -244,6 +253,8 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     q16 = hori_dtype == "uint16"
     if q16 and (svf_only or topo_only):
         raise ValueError("'svf_only' / 'topo_only' cannot be combined with hori_dtype=\"uint16\": there is no horizon to encode")
+    if hori_dist and (svf_only or topo_only):
+        raise ValueError("'svf_only' / 'topo_only' cannot be combined with 'hori_dist': there is no horizon to return it with")
 
     # Ensure that passed arrays are contiguous in memory (horizon.pyx:159-163)
     vert_grid = np.ascontiguousarray(vert_grid)
@@ -262,6 +273,9 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     if rows is not None and hori_buffer is not None:
         hori_buffer.fill(Q16_NAN if q16 else np.nan)   # only a slab is written; every cell is written otherwise
                                    # (masked ones get hori_fill), so the 18 GB pre-fill is skipped
+    dist_buffer = np.empty(hori_shape, dtype=np.float32) if hori_dist else None
+    if rows is not None and dist_buffer is not None:
+        dist_buffer.fill(np.nan)
 
     opts = hz_opts()
     opts.device = device
@@ -319,8 +333,11 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
         if planes or q16:                         # (the planes and q16 forms always take the `topo` argument)
             ex = ex or (None,)
         lay = (int(planes),) if q16 else ()       # (the q16 forms: `int planes` after hori_q)
+        if hori_dist:                             # (the _dist forms: `int hori_kind` and `dist_buffer` after hori)
+            ex = ex or (None,)
+            lay = (_hori_kind(planes, q16), ptr(dist_buffer))
         if scene is None:
-            return (L.hz_horizon_gridded_q16 if q16 else L.hz_horizon_gridded_planes if planes
+            return (L.hz_horizon_gridded_dist if hori_dist else L.hz_horizon_gridded_q16 if q16 else L.hz_horizon_gridded_planes if planes
                     else L.hz_horizon_gridded_ex if ex else L.hz_horizon_gridded)(
                 ptr(vert_grid), dem_dim_0, dem_dim_1, ptr(vec_norm), ptr(vec_north),
                 offset_0, offset_1, ptr(hori_buffer), *lay, dim_in_0, dim_in_1, azim_num,
@@ -329,7 +346,7 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
                 ptr(tri_ind_simp), num_tri_simp, elev_ang_low_lim, ptr(mask),
                 hori_fill, ray_org_elev, C.byref(o), *ex, C.byref(st))
         o.device = scene.device
-        return (L.hz_horizon_gridded_scene_q16 if q16 else L.hz_horizon_gridded_scene_planes if planes
+        return (L.hz_horizon_gridded_scene_dist if hori_dist else L.hz_horizon_gridded_scene_q16 if q16 else L.hz_horizon_gridded_scene_planes if planes
                 else L.hz_horizon_gridded_scene_ex if ex else L.hz_horizon_gridded_scene)(
             scene._h, ptr(vec_norm), ptr(vec_north), offset_0, offset_1,
             ptr(hori_buffer), *lay, dim_in_0, dim_in_1, azim_num, dist_search, hori_acc,
@@ -386,11 +403,112 @@ def horizon_gridded(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north,
     for i in range(azim_num):
         azim[i] = ((2 * np.pi) / azim_num * i)
 
+    head = (hori_buffer, dist_buffer, azim) if hori_dist else (hori_buffer, azim)
     if maps is not None:
-        return hori_buffer, azim, maps
+        return head + (maps,)
     if svf is not None:
-        return hori_buffer, azim, svf
-    return hori_buffer, azim
+        return head + (svf,)
+    return head
+
+
+def horizon_distance(vert_grid, dem_dim_0, dem_dim_1, vec_norm, vec_north, offset_0, offset_1,
+                     hori, dist_search, hori_acc=0.25, geom_type="grid",
+                     vert_simp=np.array([0.0, 0.0, 0.0, 0.0], dtype=np.float32),
+                     num_vert_simp=1,
+                     tri_ind_simp=np.array([0, 0, 0, 0], dtype=np.int32),
+                     num_tri_simp=1, elev_ang_low_lim=-15.0, mask=None, ray_org_elev=0.01,
+                     *, device=0, scene=None, layout="cell_major", rows=None, _chunk_rows=0):
+    """Distance to the horizon for a gridded horizon (not in the reference, which has it for locations only).
+
+    ``hori`` is a horizon of the inner domain as ``horizon_gridded`` returns it: float32 [radian] or the uint16 codes of
+    ``quantise``, (y, x, azim_num) or, with ``layout="azim_major"``, (azim_num, y, x); ``azim_num`` is read from its shape.
+    The other arguments are those ``hori`` was computed with (``hori_acc``, ``elev_ang_low_lim`` and ``dist_search`` fix the
+    elevation table and the ray length).  Returns the distance [metre], float32 of the shape of ``hori``.
+
+    Meaning (clause 16), that of the reference's ``hori_dist_out``: the closest hit of the last ray
+    that hit.  For a cell with ``mask == 1`` and a horizon value h (a code is decoded first), the ray is the one of the
+    table entry ``hori_acc`` (five entries) below the last entry that is <= h -- for ``guess_constant`` exactly the last
+    ray that hit -- and the distance is that of the closest triangle (DEM mesh or outer TIN) within ``dist_search``.  A
+    nearer, lower ridge that also rises above h - ``hori_acc`` is what is reported, not the far range behind it.  NaN where
+    that ray hits nothing (directions in which a small domain has no terrain), where h is NaN (outside a ``rows`` slab)
+    and where ``mask != 1``.
+
+    Keyword-only: ``device``, ``scene`` (a prebuilt ``Scene``), ``layout``, ``rows`` ((begin, end) slab of inner-domain rows to
+    compute; the rest of the result is NaN)."""
+    global last_stats
+    _check_f32(vert_grid, 1, "vert_grid")
+    _check_f32(vec_norm, 3, "vec_norm")
+    _check_f32(vec_north, 3, "vec_north")
+    _check_f32(vert_simp, 1, "vert_simp")
+    if not isinstance(tri_ind_simp, np.ndarray) or tri_ind_simp.ndim != 1 or tri_ind_simp.dtype != np.int32:
+        raise ValueError("Buffer dtype mismatch, expected 'int32_t' for tri_ind_simp")
+    if mask is not None and (not isinstance(mask, np.ndarray) or mask.ndim != 2):
+        raise ValueError("Buffer has wrong number of dimensions (expected 2) for mask")
+    if not isinstance(hori, np.ndarray):
+        raise TypeError("Argument 'hori' has incorrect type (expected numpy.ndarray, got %s)" % type(hori).__name__)
+    if hori.ndim != 3:
+        raise ValueError("Buffer has wrong number of dimensions (expected 3, got %d)" % hori.ndim)
+    if hori.dtype not in (np.float32, np.uint16):
+        raise ValueError("Buffer dtype mismatch, expected 'float32_t' or 'uint16_t' but got '%s'" % hori.dtype.name)
+    planes = check_layout(layout)
+    if mask is None:
+        mask = np.ones(vec_norm.shape[:2], dtype=np.uint8)
+    dim_in_0, dim_in_1 = vec_norm.shape[0], vec_norm.shape[1]
+    azim_num = hori.shape[0] if planes else hori.shape[2]
+    V.run((
+        (ValueError, "inconsistency between input arguments vert_grid, dem_dim_0 and dem_dim_1",
+         lambda: not V.fits_grid(len(vert_grid), dem_dim_0, dem_dim_1)),
+        (ValueError, "inconsistency between input arguments dem_dim_0, dem_dim_1, offset_0, offset_1 and vec_norm",
+         lambda: not V.window_inside(offset_0, offset_1, vec_norm.shape, dem_dim_0, dem_dim_1)),
+        (ValueError, V.MSG_NORTH, lambda: not V.same_leading_shape((vec_norm, vec_north), 3, 3)),
+        (ValueError, "Inconsistent/incorrect shape of 'hori'",
+         lambda: azim_num < 1 or (hori.shape[1:] if planes else hori.shape[:2]) != (dim_in_0, dim_in_1)),
+        (ValueError, V.MSG_GEOM, lambda: geom_type not in V.GEOMETRIES),
+        (ValueError, "inconsistency between input arguments vert_simp and num_vert_simp", lambda: len(vert_simp) < num_vert_simp * 3),
+        (ValueError, "inconsistency between input arguments tri_ind_simp and num_tri_simp", lambda: len(tri_ind_simp) < num_tri_simp * 3),
+        (ValueError, "triangle indices of simplified outer domain exceed number of vertices",
+         lambda: tri_ind_simp.max() > num_vert_simp - 1),
+        (ValueError, V.MSG_ACC, lambda: hori_acc > 10.0),
+        (ValueError, "shape of mask is inconsistent with other input", lambda: mask.shape[:2] != vec_norm.shape[:2]),
+        (TypeError, V.MSG_MASK_TYPE, lambda: mask.dtype != "uint8"),
+        (TypeError, V.MSG_ELEV, lambda: ray_org_elev < 0.005),
+        (ValueError, V.MSG_DIM_LIMIT, lambda: max(dem_dim_0, dem_dim_1) > V.DIM_LIMIT),
+    ))
+    opts = hz_opts()
+    opts.device = device if scene is None else scene.device
+    opts.chunk_rows = _chunk_rows
+    if rows is not None:
+        if len(rows) != 2 or not (0 <= int(rows[0]) < int(rows[1]) <= dim_in_0):
+            raise ValueError("'rows' must be (begin, end) with 0 <= begin < end <= %d" % dim_in_0)
+        opts.row_begin, opts.row_end = int(rows[0]), int(rows[1])
+
+    vert_grid = np.ascontiguousarray(vert_grid)
+    vec_norm = np.ascontiguousarray(vec_norm)
+    vec_north = np.ascontiguousarray(vec_north)
+    vert_simp = np.ascontiguousarray(vert_simp)
+    tri_ind_simp = np.ascontiguousarray(tri_ind_simp)
+    mask = np.ascontiguousarray(mask)
+    hori = np.ascontiguousarray(hori)
+    dist = np.empty(hori.shape, dtype=np.float32)
+    if rows is not None:
+        dist.fill(np.nan)           # only a slab is written
+    kind = _hori_kind(planes, hori.dtype == np.uint16)
+    stats = hz_stats()
+    L = _lib.lib()
+    if scene is None:
+        rc = L.hz_horizon_distance(
+            ptr(vert_grid), dem_dim_0, dem_dim_1, ptr(hori), kind, ptr(dist), ptr(vec_norm), ptr(vec_north),
+            offset_0, offset_1, dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, geom_type.encode("utf-8"),
+            ptr(vert_simp), num_vert_simp, ptr(tri_ind_simp), num_tri_simp, elev_ang_low_lim, ptr(mask), ray_org_elev,
+            C.byref(opts), C.byref(stats))
+    else:
+        rc = L.hz_horizon_distance_scene(
+            scene._h, ptr(hori), kind, ptr(dist), ptr(vec_norm), ptr(vec_north), offset_0, offset_1,
+            dim_in_0, dim_in_1, azim_num, dist_search, hori_acc, elev_ang_low_lim, ptr(mask), ray_org_elev,
+            C.byref(opts), C.byref(stats))
+    _lib.check(rc)
+    last_stats = stats.as_dict()
+    return dist
 
 
 def horizon_locations(vert_grid, dem_dim_0, dem_dim_1, coords, vec_norm, vec_north,

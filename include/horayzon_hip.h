@@ -330,6 +330,71 @@ int hz_horizon_gridded_scene_q16(const hz_scene *scene,
                                  float hori_fill, float ray_org_elev,
                                  const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
 
+/* ------------------------------------------------------------------------- */
+/* The distance to the horizon of a gridded horizon (additive; DESIGN.md section 4, clause 16).  The reference    */
+/* has it only for locations (the *_hori_dist variants, horizon_comp.cpp:519-612); the meaning is theirs: the      */
+/* closest hit of the last ray that hit.  Per cell with mask == 1, azimuth a and horizon value h (float32; a code  */
+/* is decoded first):  j = max{ i : elev_ang[i] <= h } in the ascending table of hz_horizon_tables (-1: none),      */
+/* k = max(j - 5, 0); the ray of table entry k and azimuth a, direction and origin as the gridded horizon forms    */
+/* them; the distance [metre] is the minimum t over all triangles (DEM mesh and outer TIN) accepted with           */
+/* tfar = dist_search.  NaN where that ray hits nothing, where h is NaN and where mask != 1.  A nearer, lower      */
+/* ridge that also rises above h - hori_acc is what is reported.                                                    */
+/* hori_kind: HZ_HORI_PLANES and HZ_HORI_U16 or'ed -- f32[rows][dim_in_1][azim_num] (0), f32[azim_num][rows]        */
+/* [dim_in_1] (1), and the same two of 16-bit codes (2, 3).  `dist` is float32 in the layout of `hori`.  Both may  */
+/* be host or device memory; rows, row slabs (only the slab is read and written), opts->hori_is_slab (for hori     */
+/* AND dist), inputs_are_slab and chunk_rows mean what they mean for hz_horizon_gridded_planes.  Two device        */
+/* arrays are one launch; a host side moves through a bounded device buffer chunk by chunk.  hz_stats: num_rays    */
+/* (distance rays), num_cells, t_kernel_s, t_h2d_s, t_d2h_s, t_total_s, scratch_bytes.                              */
+/* ------------------------------------------------------------------------- */
+#define HZ_HORI_F32 0
+#define HZ_HORI_PLANES 1
+#define HZ_HORI_U16 2
+int hz_horizon_distance(const float *vert_grid, int dem_dim_0, int dem_dim_1,
+                        const void *hori, int hori_kind, float *dist,
+                        const float *vec_norm, const float *vec_north,
+                        int offset_0, int offset_1, int dim_in_0, int dim_in_1,
+                        int azim_num, float dist_search, float hori_acc,
+                        const char *geom_type,
+                        const float *vert_simp, int num_vert_simp,
+                        const int32_t *tri_ind_simp, int num_tri_simp,
+                        float elev_ang_low_lim, const uint8_t *mask, float ray_org_elev,
+                        const hz_opts *opts, hz_stats *stats);
+int hz_horizon_distance_scene(const hz_scene *scene,
+                              const void *hori, int hori_kind, float *dist,
+                              const float *vec_norm, const float *vec_north,
+                              int offset_0, int offset_1, int dim_in_0, int dim_in_1,
+                              int azim_num, float dist_search, float hori_acc,
+                              float elev_ang_low_lim, const uint8_t *mask, float ray_org_elev,
+                              const hz_opts *opts, hz_stats *stats);
+/* The gridded horizon of any kind (hz_horizon_gridded_ex / _planes / _q16 by hori_kind) PLUS its distances in      */
+/* dist_buffer f32, cell-major or planes as hori_kind says.  Inside the chunk loop the distance kernel runs on the   */
+/* float32 chunk after it was traced and reduced and before it is laid out or encoded, so dist_buffer equals         */
+/* hz_horizon_distance on the float32 horizon of the call, word for word -- for 16-bit codes too -- and `hori` and    */
+/* the maps are those of the call without distances.  opts->skip_hori is HZ_ERR_ARG.  hz_stats: num_rays and          */
+/* t_kernel_s include the distance rays and their kernel, t_d2h_s the copies of a host dist_buffer.                  */
+int hz_horizon_gridded_dist(const float *vert_grid, int dem_dim_0, int dem_dim_1,
+                            const float *vec_norm, const float *vec_north,
+                            int offset_0, int offset_1,
+                            void *hori, int hori_kind, float *dist_buffer,
+                            int dim_in_0, int dim_in_1,
+                            int azim_num, float dist_search, float hori_acc,
+                            const char *ray_algorithm, const char *geom_type,
+                            const float *vert_simp, int num_vert_simp,
+                            const int32_t *tri_ind_simp, int num_tri_simp,
+                            float elev_ang_low_lim, const uint8_t *mask,
+                            float hori_fill, float ray_org_elev,
+                            const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+int hz_horizon_gridded_scene_dist(const hz_scene *scene,
+                                  const float *vec_norm, const float *vec_north,
+                                  int offset_0, int offset_1,
+                                  void *hori, int hori_kind, float *dist_buffer,
+                                  int dim_in_0, int dim_in_1,
+                                  int azim_num, float dist_search, float hori_acc,
+                                  const char *ray_algorithm,
+                                  float elev_ang_low_lim, const uint8_t *mask,
+                                  float hori_fill, float ray_org_elev,
+                                  const hz_opts *opts, const hz_topo_out *topo, hz_stats *stats);
+
 /* Horizon (and optionally distance to the horizon) for arbitrary locations; argument list     */
 /* mirrors horizon_locations_comp (horizon_comp.h:22-34, horizon_comp.cpp:828-1094).           */
 /* coords f32[num_loc][3], vec_norm / vec_north f32[num_loc][3], ray_org_elev f32[num_loc],    */
@@ -400,7 +465,10 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* "q16_chunk" = elements per staging chunk of hz_hori_quantise / hz_hori_dequantise (<= 0: the default),                        */
 /* "leaf_lend" = 0: the horizon kernel's fast stack runs without leaf lending (1 or < 0: the default, with it)                  */
 /* "flat_refill" = 0: guess_constant's refill runs the search state machine's if-chain (1 or < 0: the default, the branch-free */
-/* pass; it belongs to the instantiations with leaf lending, so "leaf_lend" = 0 switches it off too)                            */
+/* pass; it belongs to the instantiations with leaf lending, so "leaf_lend" = 0 switches it off too),                           */
+/* "horidist_traversal" = 0: the distance kernel of hz_horizon_distance runs hz_closest's slot order (1 or < 0: the default,   */
+/* the children of a node front to back), "horidist_block_w" = 16, 32, 64: cells per row of a wave's block in                  */
+/* hz_horizon_distance (8 or < 0: the default, 8 x 8 cells)                                                                     */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */
