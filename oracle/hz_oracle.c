@@ -6,11 +6,19 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg use it, as the
  * checker / reported CPU baseline.
  *
- * PARITY UNPINNED: the reference delegates every hit/no-hit decision to Intel
- * Embree 4 (conda-forge `embree`, version not pinned by the reference;
- * horizon_comp.cpp:5, shadow_comp.cpp:6), which is not present in
- * /root/reference and not installable here; the reference ships no tests or
- * golden vectors for this path.  This file restates
+ * EMBREE'S DECISIONS UNPINNED: the reference delegates every hit/no-hit
+ * decision to Intel Embree 4 (conda-forge `embree`, version not pinned by the
+ * reference; horizon_comp.cpp:5, shadow_comp.cpp:6), which is not installable
+ * here; the reference ships no tests or golden vectors for this path
+ * (SURVEY.md section 4, 8c).
+ * THE RESTATEMENT OF THE REFERENCE'S OWN STATEMENTS IS PINNED: `make ref`
+ * (oracle/Makefile) compiles horizon_comp.cpp and shadow_comp.cpp unmodified
+ * against stand-in Embree / TBB headers (oracle/ref/) into
+ * oracle/_ref/libhz_ref.so, where every ray is answered by orc_occluded1 /
+ * orc_closest1 of this file; tests/test_ref_driver.py requires that driver and
+ * this file's drivers to agree bit for bit and ray for ray (DESIGN.md
+ * section 3).  A change to a driver statement below must keep that suite green.
+ * This file restates
  *   - the reference's OWN code statement by statement, including its
  *     float/double promotion pattern:
  *       helpers            horizon_comp.cpp:26-62, shadow_comp.cpp:41-159
@@ -47,6 +55,7 @@ static int g_platform_libm = 0;
 void orc_set_libm(int platform) { g_platform_libm = platform; }
 static int g_quad_order = 0;      /* 1: second triangle of a quad as Embree's quad / grid intersector orders it */
 void orc_set_quad_order(int embree_quad) { g_quad_order = embree_quad; }
+int orc_get_quad_order(void) { return g_quad_order; }
 /* Where the tree's box tests start and end (round 5): over [-tau, tfar + tau] of the ray, tau =
  * ORC_BOX_START_PADS * pad, NOT over [0, tfar].  The float triangle test can accept a crossing that in exact arithmetic lies
  * a little behind the origin (or beyond tfar) when the ray grazes the triangle's plane (T cancels to rounding noise); a tree
@@ -751,6 +760,16 @@ void orc_closest_batch(const orc_scene *s, int64_t n, const float *org, const fl
         hit[q] = (uint8_t)closest(s, org + 3 * q, dir + 3 * q, tfar[q], mode, &t);
         dist[q] = t;
     }
+}
+
+/* single-ray forms of the two batch queries, for a caller that asks one ray at a time from its own loop (the stand-in
+ * Embree of oracle/ref/standin.cpp: the batch functions open an OpenMP region per call).  orc_closest1 leaves *dist
+ * untouched on a miss, as rtcIntersect1 leaves tfar. */
+int orc_occluded1(const orc_scene *s, const float *org, const float *dir, float tfar, int mode) {
+    return occluded(s, org, dir, tfar, mode, NULL);
+}
+int orc_closest1(const orc_scene *s, const float *org, const float *dir, float tfar, int mode, float *dist) {
+    return closest(s, org, dir, tfar, mode, dist);
 }
 
 void orc_occluded_batch(const orc_scene *s, int64_t n, const float *org,
