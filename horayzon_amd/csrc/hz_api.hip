@@ -744,6 +744,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     float ms_near = 0.0f;
 
     unsigned long long cnt[16] = {0}, n_verified = 0, n_mon_violations = 0;
+    unsigned long long refill_hist[16] = {0};      // counting instantiation: counters[HZ_CNT_REFILL ..] (hz_internal.h)
     NearMonitor mon;
     float ms = 0.0f, ms_svf = 0.0f;
     int fallbacks = 0;
@@ -783,7 +784,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
     const int n_left_launches = plan_leftover(sc, opts, std::min(chunk_rows, row_end - row_begin), dim_in_1, left_t, a);
     a.left_min = n_left_launches > 0 ? left_t[0] : 0;
     a.left_rec = n_left_launches > 0 ? (unsigned *)sc->left_buf : nullptr;
-    a.left_regroup = (opts && (opts->left_tune & 0xff) > 0) ? (opts->left_tune & 0xff) : HZ_LEFT_REGROUP;
+    a.left_regroup = (opts && (opts->left_tune & 0xff) > 0) ? (opts->left_tune & 0xff) : (regroup_rule_of(a.regroup) ? HZ_LEFT_REGROUP_REL : HZ_LEFT_REGROUP);
     a.left_key_shift = (opts && ((opts->left_tune >> 8) & 0xff) > 0) ? std::min(((opts->left_tune >> 8) & 0xff) - 1, 8) : HZ_LEFT_KEY_SHIFT;
     a.persist_grid = (opts && opts->persist_grid > 0) ? opts->persist_grid : 0;
     a.no_persist = (opts && opts->persist_grid < 0) ? 1 : 0;
@@ -1034,6 +1035,7 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
             left_cells += c[28]; left_again += c[29];
             n_verified += c[21];
             lend_tests += c[22]; lend_unhelped += c[23];
+            for (int k = 0; k < 16; k++) refill_hist[k] += c[HZ_CNT_REFILL + k];
             if (a.count_work && opts && opts->verbose >= 3) {      // per-XCD span of this launch (counting instantiation)
                 const unsigned long long t0 = ~c[20];
                 fprintf(stderr, "hz xcd spans [ms] rows %d..%d:", rb, re);
@@ -1084,6 +1086,15 @@ static int horizon_run(const Scene *sc, const float *vec_norm, const float *vec_
         fprintf(stderr, "hz leaf lending: %llu lent leaf tests, %llu leaf-step lanes with a second leaf and no helper (a = %.3f); "
                         "wave leaf steps %llu, wave node steps %llu, triangles tested %llu\n", lend_tests, lend_unhelped,
                 (lend_tests + lend_unhelped) ? (double)lend_tests / (double)(lend_tests + lend_unhelped) : 0.0, cnt[6], cnt[5], cnt[3]);
+    if (a.count_work && opts && opts->verbose >= 2) {
+        // refills of the counting instantiation by population (8 buckets of 8 lanes): how many lanes a refill serves, and how
+        // many enter the traversal behind it
+        fprintf(stderr, "hz refills (regroup rule %d) by lanes served  1-8 .. 57-64:", regroup_rule_of(a.regroup));
+        for (int k = 0; k < 8; k++) fprintf(stderr, " %llu", refill_hist[k]);
+        fprintf(stderr, "\nhz refills by lanes entering the traversal 1-8 .. 57-64:");
+        for (int k = 8; k < 16; k++) fprintf(stderr, " %llu", refill_hist[k]);
+        fprintf(stderr, "\n");
+    }
     if (opts && opts->verbose)
         print_reference_report(sc, alg, cnt[4], cnt[0], slab_cells, dim_in_0, dim_in_1, azim_num, (double)ms * 1e-3,
                                !use_near && near_opt <= 0 && !height_field && !bad_map, use_near && bad_map);
@@ -1991,6 +2002,8 @@ int hz_debug_set(const char *key, int value) {
     else if (!strcmp(key, "topo_wide")) hz::g_topo_wide.store(value != 0, std::memory_order_relaxed);
     else if (!strcmp(key, "leaf_lend")) hz::g_leaf_lend.store(value != 0, std::memory_order_relaxed);      // (< 0: the default, on)
     else if (!strcmp(key, "flat_refill")) hz::g_flat_refill.store(value != 0, std::memory_order_relaxed);  // (< 0: the default, on)
+    else if (!strcmp(key, "regroup_round")) hz::g_regroup_round.store((value < 0 || value > 63) ? HZ_REGROUP_ROUND : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "regroup_rule")) hz::g_regroup_rule.store(value != 0, std::memory_order_relaxed);  // (< 0: the default, relative)
     else if (!strcmp(key, "accum_chunk")) hz::g_accum_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "coarse_tile")) hz::g_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_chunk")) hz::g_horisun_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);

@@ -479,7 +479,8 @@ __device__ __forceinline__ void hz_load_prim(const Prim *q, float4 &q0, float4 &
 //               live in bits 0, 1 and 30).  At most one entry per level is alive: `height` entries cannot overflow.
 //   top       : LDS copy of the first ntop nodes, read only by the NODELET instantiation (else null / 0)
 //   regroup   : leave when fewer than `regroup` lanes of the wave are still traversing (and at least one
-//               lane finished in this call, so the caller can refill it)
+//               lane finished in this call, so the caller can refill it); regroup_rule says how that threshold follows
+//               the number of lanes that entered with a ray (hz_n_leave below: rule | round << 1; 0, the default: absolute)
 //   leaf_bias : the wave takes the node step when 16 * (lanes with a node) >= leaf_bias * (lanes with a leaf)
 // Scheduling inside the wave: every lane sets leaves aside (up to QLEN) and keeps descending;
 // each iteration the wave executes ONE kind of step -- the node step or the leaf step --
@@ -489,6 +490,30 @@ __device__ __forceinline__ void hz_load_prim(const Prim *q, float4 &q0, float4 &
 // ---------------------------------------------------------------------------
 struct TravCounters { unsigned nodes, tris, w_nodes, w_leaves;
 };
+#endif  // __HIPCC__
+
+// Lanes of a wave that must still be traversing for hz_trace's loop to go on (it is left below that: the ray compaction).
+//   regroup : the threshold for a full wave, 1 ... 64;  n_entry : lanes that entered the call with a ray, 1 ... 64
+//   rule 0  : absolute -- min(regroup, n_entry): a wave of 40 rays and regroup = 36 leaves after 5 decided rays, one of 30 after
+//             every single one
+//   rule 1  : relative -- (regroup * n_entry + round) >> 6: the share of decided lanes that ends the loop stays what it is for a
+//             full wave (the same value as rule 0 at n_entry = 64, for every round)
+//   round   : 0 ... 63, how the share is rounded (0: down, 32: to nearest, 63: up); rule 0 does not depend on it
+// Both give 1 <= n_leave <= n_entry (regroup <= 64): the loop only ends after a lane's ray is decided -- the caller can refill
+// it -- or when no lane traverses.  Which lanes are refilled when is schedule only; no result depends on the rule.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int hz_n_leave(int regroup, int n_entry, int rule, int round) {
+    // one form for both, so that a rule known only at run time is two scalar selects and no branch:
+    //   rule 0 = min(regroup, (64 * n_entry + round) >> 6) = min(regroup, n_entry);  rule 1 = min(64, (regroup * n_entry + round) >> 6)
+    const int cap = rule ? 64 : regroup, share = rule ? regroup : 64;
+    const int rel = (share * n_entry + round) >> 6;
+    const int cut = cap < rel ? cap : rel;
+    return cut > 1 ? cut : 1;
+}
+
+#ifdef __HIPCC__
 struct LendCounters { unsigned lent, unhelped; };     // COUNT && LEND: leaf tests done by a partner lane; leaf-step lanes with a second leaf and no helper
 struct TravState { int node, sp, pf, pm, lq0, lq1; };
 
@@ -523,7 +548,8 @@ __device__ __forceinline__ int hz_trace(const Node *__restrict__ nodes, const Pr
                                         const float4 *top, int ntop, int *stack, int tid,
                                         float ox, float oy, float oz, float dx, float dy, float dz, float tfar,
                                         float tfar_box, const RayBox &rb, TravState &t, int regroup, int leaf_bias,
-                                        TravCounters &cnt, int stack_cap, bool &overflow, LendCounters *lcnt = nullptr) {
+                                        TravCounters &cnt, int stack_cap, bool &overflow, LendCounters *lcnt = nullptr,
+                                        int regroup_rule = 0) {
     const int lane = tid & 63;
     int node = t.node, sp = t.sp, pf = t.pf, pm = t.pm, lq0 = t.lq0, lq1 = t.lq1;
     const int n_entry = __popcll(__ballot(1));   // lanes that entered with a ray
@@ -566,7 +592,7 @@ typedef __attribute__((address_space(3))) int hz_lds_int;
     // finished its ray in this call -- it can refill, so the caller always makes progress) or when none is.  A lane whose
     // ray is decided idles until then: a miss holds HZ_EMPTY and an empty queue; a hit holds HZ_EMPTY and the NUMBER of
     // the blocking leaf instead of its link in lq0 (non-negative: "no leaf queued"; never HZ_EMPTY).  No per-lane exit, no result register in the loop.
-    const int n_leave = max(min(regroup, n_entry), 1);
+    const int n_leave = hz_n_leave(regroup, n_entry, regroup_rule & 1, regroup_rule >> 1);      // (wave uniform: scalar registers)
     // The loop is rotated by hand: [queue fills + votes] once in front of it and again at the end of its body, so that the
     // wave's exit test is the loop condition itself.
     bool can_node, can_leaf;

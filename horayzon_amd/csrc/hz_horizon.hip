@@ -55,7 +55,10 @@ struct HorizonParams {
     float dist_box, neg_tau;       // dist + 2 tau and -tau (hz_common.h: where the box tests start and end), formed on the host: uniform
                                    // float arithmetic in the kernel would sit in vector registers, and there is none to spare
     int top_nodes, regroup, stack_bytes, leaf_bias, stage_bytes, hit_cache, stack_cap;
-    int pre_bytes;                 // LDS in front of the stack: the output staging buffer, or (no staging) two padding rows --
+                                   // (regroup = threshold | rule << 8 | round << 9 -- how the threshold follows the lanes that enter hz_trace with a ray,
+                                   //  hz_n_leave in hz_common.h: 0 absolute, 1 relative -- in ONE word: a second scalar register kept through the
+                                   //  traversal loop cost the production instantiation 15 more v_readlane_b32 of spilled scalars, 8 of them in the refill)
+    int pre_bytes;                // LDS in front of the stack: the output staging buffer, or (no staging) two padding rows --
                                    // the fast stack reads the rows below its sentinel together with the top (hz_trace)
     const unsigned short *near_idx;   // near-field certificates of this launch's rows (hz_near.hip) or null
     const float *near_r;
@@ -285,6 +288,9 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     s.k = 0; s.phase = PH_NEWAZ; s.ind = 0; s.prev = 0; s.pazim = 0; s.count = 0;
     s.lim_up = 0; s.lim_low = 0; s.elev_samp = 0; s.ev = 0;
     unsigned rays = 0, guards = 0, w_adv = 0;
+    // COUNT: refills of this wave by population, tallied by the lane whose number is the bucket: lanes 0 - 7 by the lanes the
+    // refill serves (1 - 8, 9 - 16, ...), lanes 8 - 15 by the lanes that enter hz_trace behind it (n_entry, same buckets)
+    unsigned refill_hist = 0;
     TravCounters tc; tc.nodes = 0; tc.tris = 0; tc.w_nodes = 0; tc.w_leaves = 0;   // COUNT only
     LendCounters lc; lc.lent = 0; lc.unhelped = 0;                                  // COUNT && LEND only
     const unsigned cells_cnt = (in_dom && !done && !LEFT) ? 1u : 0u;
@@ -363,6 +369,8 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
 
         if (__ballot(!done) == 0ull) break;
         // ---- refill: lanes without a ray take the next sample of their search -----------------
+        const int n_refill = COUNT ? __popcll(__ballot(!done && !ray_active)) : 0;
+        if (COUNT && n_refill > 0 && lane == ((n_refill - 1) >> 3)) refill_hist++;
         if (!done && !ray_active) {
             if (COUNT) HZ_WAVE_TICK(w_adv, lane);
             // (the per-cell addresses are rebuilt from `cert` HERE, at every refill: the empty asm keeps the compiler from
@@ -444,10 +452,14 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
         }
         // ---- traversal (hz_common.h: speculative while-while, one postponed leaf per lane) ------
         bool start_v = false, viol = false;
+        if (COUNT && n_refill > 0) {
+            const int n_enter = __popcll(__ballot(ray_active));
+            if (n_enter > 0 && lane == 8 + ((n_enter - 1) >> 3)) refill_hist++;
+        }
         if (ray_active) {
             int r;
             r = hz_trace<HZ_TPB, COUNT, HZ_QLEN, NODELET, LEVELSTACK, LEND>(p.sv.nodes, p.sv.prims, top, ntop, stack, tid, ox, oy, oz,
-                                                 dx, dy, dz, tfar, p.dist_box, rb, ts, p.regroup, p.leaf_bias, tc, p.stack_cap, overflow, &lc);
+                                                 dx, dy, dz, tfar, p.dist_box, rb, ts, p.regroup & 0xff, p.leaf_bias, tc, p.stack_cap, overflow, &lc, p.regroup >> 8);
             if (r == 0 && second) {                      // nothing in the cached subtree: full traversal
                 second = false; hz_trav_reset(ts);
             } else if (COUNT && want_v && r != 2) {
@@ -500,6 +512,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
             if (LEND) { atomicAdd(&p.counters[22], ln); atomicAdd(&p.counters[23], un); }
         }
     }
+    if (COUNT && lane < 16 && refill_hist != 0u) atomicAdd(&p.counters[HZ_CNT_REFILL + lane], (unsigned long long)refill_hist);
     if (COUNT) {
         // when did the last wave of each XCD finish?  (counters[12 + xcc] = latest end, counters[20] = ~earliest start, on
         // the 100 MHz real-time counter; HZ_XCD_TRACE=1 prints the spans: the 8 XCDs own fixed regions of the tile)
@@ -525,6 +538,8 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
 
 std::atomic<int> g_leaf_lend{1};      // hz_debug_set("leaf_lend", 0 | 1) (hz_internal.h)
 std::atomic<int> g_flat_refill{1};    // hz_debug_set("flat_refill", 0 | 1) (hz_internal.h)
+std::atomic<int> g_regroup_rule{1};   // hz_debug_set("regroup_rule", 0 | 1) (hz_internal.h)
+std::atomic<int> g_regroup_round{HZ_REGROUP_ROUND};   // hz_debug_set("regroup_round", 0 ... 63)
 
 // Workgroups of `func` (HZ_TPB threads, `lds` bytes of dynamic LDS) the current device keeps resident at once; 0: unknown.  Asked once
 // per (kernel, LDS size, device): the occupancy query and hipGetDeviceProperties are host-side work in front of every launch otherwise.
@@ -732,9 +747,16 @@ int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *u
     // are traversing (40 until round 5: re-swept after the loop rewrite, profiles/r05/ab_tri_fma_and_regroup_sweep.log: 32 - 36
     // beat 40 by 1.2 %, 28 and 40 tie, 16 costs 7 %); leaf step when 24 n_leaf > 16 n_node.  opts.regroup = threshold | bias << 8.
     // (<= 0: the default -- a zeroed hz_opts must not switch the ray compaction off: 2.9 s instead of 2.15 s per tile)
-    p.regroup = (a.regroup <= 0) ? 36 : std::min(a.regroup & 0xff, 64);
+    // The threshold follows the lanes that enter hz_trace with a ray (rule 1 of hz_n_leave, hz_common.h; hz_debug_set("regroup_rule", 0)
+    // or bit 16 of opts.regroup: rule 0, the absolute threshold of the rounds before, with its default of 36).  Under rule 1 a wave
+    // with few rays left no longer pays a refill per decided ray, which is what held the threshold down: 44 - 48 beat 36 by 1.7 %,
+    // 52 by 0.9 %, 56 loses 2 % (rule 0: 44 gains 0.3 %, 48 loses 1.3 %; profiles/r09/ab_regroup_rule.log).
+    const int rule = regroup_rule_of(a.regroup);
+    const int rg = (a.regroup > 0) ? (a.regroup & 0xffff) : a.regroup;
+    p.regroup = (rg <= 0) ? (rule ? 44 : 36) : std::min(rg & 0xff, 64);
     if (a.left_mode && a.left_regroup > 0) p.regroup = std::min(a.left_regroup, 64);
-    p.leaf_bias = (a.regroup >= 256) ? (a.regroup >> 8) : 24;      // (20 until round 4: re-swept after the node step lost 18 instructions, profiles/r04/regroup_sweep.log)
+    p.regroup |= (rule << 8) | ((g_regroup_round.load(std::memory_order_relaxed) & 63) << 9);
+    p.leaf_bias = (rg >= 256) ? (rg >> 8) : 24;      // (20 until round 4: re-swept after the node step lost 18 instructions, profiles/r04/regroup_sweep.log)
     p.hit_cache = (a.hit_cache != 0) ? 1 : 0;
     p.near_idx = a.near_idx; p.near_r = a.near_r;
     p.verify_near = (a.verify_near > 0 && a.near_idx != nullptr) ? 1 : 0;

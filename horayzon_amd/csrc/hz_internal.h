@@ -29,6 +29,15 @@ int set_error(int code, const char *fmt, ...);
 extern std::atomic<int> g_shadow_fast_cap;   // entries of k_shadow_refill's fast stack (default HZ_SHADOW_FAST_CAP_DEFAULT; 0: level stack only)
 extern std::atomic<int> g_leaf_lend;         // 1 (default): k_horizon's fast stack lends idle lanes to the partner lane's second queued leaf (hz_trace, LEND)
 extern std::atomic<int> g_flat_refill;       // 1 (default): guess_constant's fast-stack instantiations refill through advance_guess_flat (hz_search.h, FLAT)
+extern std::atomic<int> g_regroup_rule;      // 1 (default): k_horizon's compaction threshold scales with the lanes that enter hz_trace (hz_n_leave, rule 1); 0: absolute
+// (rounding of the relative threshold: 8 / 16 / 24 / 32 / 48 / 63 all run 1.158 - 1.166 s where the absolute rule runs 1.182 - 1.186 s,
+//  profiles/r09/ab_regroup_rule.log call 5 -- time does not tell them apart; 48 had the narrowest range, 1.158 - 1.159 s)
+#define HZ_REGROUP_ROUND 48
+extern std::atomic<int> g_regroup_round;     // rule 1: the rounding addend of hz_n_leave, 0 ... 63 (default HZ_REGROUP_ROUND)
+// (bit 16 of hz_opts.regroup forces rule 0 for one call: the A/B inside one library and process)
+inline int regroup_rule_of(int opts_regroup) {
+    return (g_regroup_rule.load(std::memory_order_relaxed) != 0 && !(opts_regroup > 0 && (opts_regroup & 0x10000))) ? 1 : 0;
+}
 extern std::atomic<int> g_topo_wide;         // 1: the reductions over the azimuth axis use the fallback kernel k_topo_wide
 extern std::atomic<int> g_accum_chunk;       // > 0: sun positions per chunk of hz_terrain_accumulate (default 0: from the memory budget)
 extern std::atomic<int> g_coarse_tile;       // > 0: cells of k_coarse_reduce's LDS tile, at most the default (hz_subgrid.hip; default 0)
@@ -172,9 +181,11 @@ struct HorizonArgs {
 // follow-up launches (hz_opts.left_tune; swept in round 6, profiles/r06/ab_leftover_tune.log: 73 ms against 76 with classes of one
 // azimuth and the production launch's threshold of 36; classes of 32 azimuths: 95 ms)
 #define HZ_LEFT_KEY_SHIFT 3              // log2 of the width of the azimuths-left classes of the sort key: 8 azimuths
-#define HZ_LEFT_REGROUP 24               // compaction threshold in lanes
+#define HZ_LEFT_REGROUP 24               // compaction threshold in lanes under rule 0 of hz_n_leave (the absolute threshold) ...
+#define HZ_LEFT_REGROUP_REL 32           // ... and under rule 1 (profiles/r09/ab_regroup_rule.log: follow-up launch 73.0 -> 71.1 ms, 40 and 48 tie, 56 loses)
 #define HZ_CNT_LEFT 32                   // first u64 word of the leftover control words
-#define HZ_CNT_N 64                      // u64 words in front of the redo list
+#define HZ_CNT_REFILL 64                 // counting instantiation: [64..71] refills by lanes served (8 buckets of 8), [72..79] by lanes entering hz_trace behind them
+#define HZ_CNT_N 80                      // u64 words in front of the redo list
 #define HZ_LEFT_WORDS 16                 // 32-bit words per leftover record
 #define HZ_REDO_CAP 16384                // 8 x 8 blocks of one launch that can be repeated one by one after a stack overflow
 int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *used_level_stack = nullptr);

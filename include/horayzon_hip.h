@@ -48,6 +48,8 @@ typedef struct hz_opts {
     int32_t top_nodes;     /* > 0: stage that many top-of-tree BVH nodes in LDS (guess_constant;   */
                            /*   measured 2 % slower than L1 reads, so <= 0 means none)            */
     int32_t regroup;       /* wave regroup threshold in lanes (<= 0: default)  */
+                           /*   | leaf-vote bias << 8 | 0x10000: the threshold  */
+                           /*   is absolute ("regroup_rule" of hz_debug_set)    */
     int32_t count_work;    /* 1: also count BVH nodes / triangle tests (slow)  */
     int32_t no_hit_cache;  /* 0 (default): rays expected to be blocked first walk the subtree  */
                            /*   that blocked the cell's previous ray; 1: always start at the root */
@@ -466,6 +468,10 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* "leaf_lend" = 0: the horizon kernel's fast stack runs without leaf lending (1 or < 0: the default, with it)                  */
 /* "flat_refill" = 0: guess_constant's refill runs the search state machine's if-chain (1 or < 0: the default, the branch-free */
 /* pass; it belongs to the instantiations with leaf lending, so "leaf_lend" = 0 switches it off too),                           */
+/* "regroup_rule" = 0: the horizon kernel's ray-compaction threshold is absolute -- a wave leaves the traversal loop when fewer */
+/* than min(regroup, lanes that entered with a ray) still traverse, regroup 36 by default -- (1 or < 0: the default, the         */
+/* threshold scales with the lanes that entered, regroup 44 by default; bit 16 of hz_opts.regroup forces 0 for one call),       */
+/* "regroup_round" = 0 ... 63: the rounding addend of that scaled threshold, (regroup * lanes + round) >> 6 (< 0: the default),  */
 /* "horidist_traversal" = 0: the distance kernel of hz_horizon_distance runs hz_closest's slot order (1 or < 0: the default,   */
 /* the children of a node front to back), "horidist_block_w" = 16, 32, 64: cells per row of a wave's block in                  */
 /* hz_horizon_distance (8 or < 0: the default, 8 x 8 cells)                                                                     */

@@ -21,7 +21,7 @@ ap.add_argument("--count", action="store_true")
 ap.add_argument("--count-all", action="store_true")
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--top", type=int, default=-1)
-ap.add_argument("--regroup", type=int, default=-1)
+ap.add_argument("--regroup", type=lambda x: int(x, 0), default=-1, help="hz_opts.regroup: threshold | vote bias << 8 | 0x10000 (force the absolute threshold, rule 0 of hz_n_leave)")
 ap.add_argument("--hit-cache", type=int, default=1)
 ap.add_argument("--stack", type=int, default=0)
 ap.add_argument("--no-near", action="store_true", help="switch the near-field certificates off")
@@ -31,6 +31,8 @@ ap.add_argument("--pgrid", type=int, default=0, help="hz_opts.persist_grid")
 ap.add_argument("--tune", type=lambda x: int(x, 0), default=0, help="hz_opts.left_tune")
 ap.add_argument("--lend", type=int, default=-1, help="hz_debug_set(\"leaf_lend\", 0 | 1): leaf lending in the leaf step (-1: the default, on)")
 ap.add_argument("--flat", type=int, default=-1, help="hz_debug_set(\"flat_refill\", 0 | 1): the branch-free refill of guess_constant (-1: the default, on)")
+ap.add_argument("--rule", type=int, default=-1, help="hz_debug_set(\"regroup_rule\", 0 | 1): the compaction threshold is absolute / scales with the wave's live lanes (-1: the default, 1)")
+ap.add_argument("--round", type=int, default=-1, help="hz_debug_set(\"regroup_round\", 0 ... 63): rounding addend of the relative threshold (-1: the default)")
 ap.add_argument("--rows", type=int, default=0, help="only the middle ROWS rows of the window")
 ap.add_argument("--verbose", type=int, default=0, help="hz_opts.verbose (2: diagnostics of the counting instantiation to stderr)")
 ap.add_argument("--verify-sample", type=int, default=0, help="production kernel with the sampled certificate check: one of every N shortened rays")
@@ -50,6 +52,12 @@ if args.lend >= 0:
 if args.flat >= 0:
     from horayzon_amd import _lib
     _lib.check(_lib.lib().hz_debug_set(b"flat_refill", args.flat))
+if args.rule >= 0:
+    from horayzon_amd import _lib
+    _lib.check(_lib.lib().hz_debug_set(b"regroup_rule", args.rule))
+if args.round >= 0:
+    from horayzon_amd import _lib
+    _lib.check(_lib.lib().hz_debug_set(b"regroup_round", args.round))
 rows = ((w - args.rows) // 2, (w - args.rows) // 2 + args.rows) if 0 < args.rows < w else None
 sc = hz.Scene.create(g["vert_grid"], n, n)
 print("scene create %.2fs" % (time.time() - t), json.dumps(sc.stats), flush=True)
