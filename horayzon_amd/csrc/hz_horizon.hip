@@ -28,7 +28,7 @@
 //
 // The float/double promotion pattern of the reference's index arithmetic is
 // reproduced exactly (hard part 2); tables are built on the
-// host with the reference's expressions (hz_api.hip) and only read here.
+// host with the reference's expressions (hz_api_horizon.hip) and only read here.
 #include "hz_search.h"
 #include <vector>
 
@@ -68,7 +68,7 @@ struct HorizonParams {
     unsigned long long *counters;
     const int *tile_list;          // null, or the n_list blocks (workgroup number * 4 + wave, of the full launch) to repeat
     int n_list;
-    int *redo_list;                // !LEVELSTACK: waves whose stack overflowed append their block here (count: counters[8])
+    int *redo_list;                // !LEVELSTACK: waves whose stack overflowed append their block here (count: counters[HZ_CNT_OVERFLOW])
     // Leftover cells (rounds 5 - 6): a block ENDS when at most left_min of its cells are unfinished; those lanes append their cell's state
     // (HZ_LEFT_WORDS words per cell) to the OUT region of left_rec (out_ctl[0] = slots allocated there), and a later launch (left_mode =
     // level >= 1, the LEFT instantiation) finishes them, 64 records per wave -- and may hand over again, to the next level's region
@@ -87,7 +87,7 @@ struct HorizonParams {
 
 // LDS: [ per-lane stacks int[depth][256] | output staging float[4][256] | top-of-tree nodelet Node[top_nodes] ]
 // LEVELSTACK: the traversal's stack discipline (hz_common.h).  false = one LDS entry per pending sibling: fewest VALU
-// instructions, `stack_cap` entries, overflow flagged in counters[8]; true = one entry per tree level, cannot overflow.
+// instructions, `stack_cap` entries, overflow flagged in counters[HZ_CNT_OVERFLOW]; true = one entry per tree level, cannot overflow.
 // (the counting instantiation carries ~20 more live values: at 5 workgroups per CU it spilled 10 - 22 VGPRs, so it is built
 //  for 4.  Its tallies -- rays, node visits, triangle tests, wave iterations -- are functions of the lanes' states only, not
 //  of the schedule, so they are the production launch's numbers: the ray counts of the two instantiations are compared by the tests.)
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     // launch-local cell number: the only per-cell address state kept across the traversal (the output pointer
     // and the certificate row are rebuilt from it at every refill: 1 VGPR instead of 2 + 2)
     const unsigned cert = in_dom ? (unsigned)(i - p.row_begin) * (unsigned)p.dim_in_1 + (unsigned)j : 0u;
-    // (the certificate monitor -- a counting launch NEXT TO the production launch, hz_api.hip -- stores into one scratch row: the
+    // (the certificate monitor -- a counting launch NEXT TO the production launch, hz_api_horizon.hip -- stores into one scratch row: the
     //  rows of `hori` belong to the production launch)
     const bool to_scratch = COUNT && p.scratch_row != nullptr;
     float *const hori0 = to_scratch ? p.scratch_row : p.hori + (size_t)p.row_begin * p.dim_in_1 * (size_t)t.azim_num;   // first cell of this launch
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
                     left_on = 0; left_min = 0;
                     if (base + (unsigned)lane < p.left_out_cap) out_rec[(size_t)(base + (unsigned)lane) * HZ_LEFT_WORDS] = 0xffffffffu;
                 } else {
-                    if (lane == 0) atomicAdd(&p.counters[LEFT ? 29 : 28], (unsigned long long)n);      // (statistics: hz_stats.left_cells / left_again)
+                    if (lane == 0) atomicAdd(&p.counters[LEFT ? HZ_CNT_LEFT_AGAIN : HZ_CNT_LEFT_CELLS], (unsigned long long)n);      // (statistics: hz_stats.left_cells / left_again)
                     if (!done) {
                         const unsigned rank = (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(um >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)um, 0u));
                         const unsigned flags = (unsigned)s.phase | (last_hit ? 0x100u : 0u) | (ray_active ? 0x200u : 0u) | ((guards != 0u || had_guard) ? 0x400u : 0u);
@@ -497,38 +497,38 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     if (wave_overflowed) {
         if (lane == 0) {
             // (LEFT: the GROUP is computed again -- its records are only read here -- and has a count and a list of its own)
-            const unsigned long long slot = atomicAdd(&p.counters[LEFT ? 30 : 8], 1ull);
+            const unsigned long long slot = atomicAdd(&p.counters[LEFT ? HZ_CNT_LEFT_OVERFLOW : HZ_CNT_OVERFLOW], 1ull);
             if (slot < (unsigned long long)HZ_REDO_CAP) p.redo_list[(LEFT ? HZ_REDO_CAP : 0) + (int)slot] = blk;
         }
     } else {
     const int guard_cells = __popcll(__ballot(guards != 0u && !(LEFT && had_guard)));   // cells where the reference's search would not terminate (a leftover cell: counted once)
     if (lane == 0) {
-        if (r) atomicAdd(&p.counters[0], r);
-        if (g) { atomicAdd(&p.counters[1], g); atomicAdd(&p.counters[11], (unsigned long long)guard_cells); }
-        if (cc) atomicAdd(&p.counters[4], cc);
+        if (r) atomicAdd(&p.counters[HZ_CNT_RAYS], r);
+        if (g) { atomicAdd(&p.counters[HZ_CNT_GUARDS], g); atomicAdd(&p.counters[HZ_CNT_GUARD_CELLS], (unsigned long long)guard_cells); }
+        if (cc) atomicAdd(&p.counters[HZ_CNT_CELLS], cc);
         if (COUNT) {
-            atomicAdd(&p.counters[2], nc); atomicAdd(&p.counters[3], tcn);
-            atomicAdd(&p.counters[5], wn); atomicAdd(&p.counters[6], wl); atomicAdd(&p.counters[7], wa);
-            if (LEND) { atomicAdd(&p.counters[22], ln); atomicAdd(&p.counters[23], un); }
+            atomicAdd(&p.counters[HZ_CNT_NODES], nc); atomicAdd(&p.counters[HZ_CNT_TRIS], tcn);
+            atomicAdd(&p.counters[HZ_CNT_WAVE_NODE], wn); atomicAdd(&p.counters[HZ_CNT_WAVE_LEAF], wl); atomicAdd(&p.counters[HZ_CNT_WAVE_REFILL], wa);
+            if (LEND) { atomicAdd(&p.counters[HZ_CNT_LENT], ln); atomicAdd(&p.counters[HZ_CNT_UNHELPED], un); }
         }
     }
     if (COUNT && lane < 16 && refill_hist != 0u) atomicAdd(&p.counters[HZ_CNT_REFILL + lane], (unsigned long long)refill_hist);
     if (COUNT) {
-        // when did the last wave of each XCD finish?  (counters[12 + xcc] = latest end, counters[20] = ~earliest start, on
+        // when did the last wave of each XCD finish?  (counters[HZ_CNT_XCD_END + xcc] = latest end, counters[HZ_CNT_START] = ~earliest start, on
         // the 100 MHz real-time counter; HZ_XCD_TRACE=1 prints the spans: the 8 XCDs own fixed regions of the tile)
         if (lane == 0) {
             const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;      // HW_REG_XCC_ID, bits 3:0
-            atomicMax(&p.counters[12 + xcc], (unsigned long long)wall_clock64());
-            atomicMax(&p.counters[20], ~t_start);
+            atomicMax(&p.counters[HZ_CNT_XCD_END + xcc], (unsigned long long)wall_clock64());
+            atomicMax(&p.counters[HZ_CNT_START], ~t_start);
         }
     }
     if (COUNT) {
         unsigned long long sh = shortened;
         for (int off = 32; off > 0; off >>= 1) sh += __shfl_xor(sh, off);
         if (lane == 0) {
-            if (sh) atomicAdd(&p.counters[9], sh);
-            if (w_violations) atomicAdd(&p.counters[10], (unsigned long long)w_violations);
-            if (w_verified) atomicAdd(&p.counters[21], (unsigned long long)w_verified);
+            if (sh) atomicAdd(&p.counters[HZ_CNT_SHORTENED], sh);
+            if (w_violations) atomicAdd(&p.counters[HZ_CNT_VIOLATIONS], (unsigned long long)w_violations);
+            if (w_verified) atomicAdd(&p.counters[HZ_CNT_VERIFIED], (unsigned long long)w_verified);
         }
     }
     }   // (!wave_overflowed)
@@ -714,7 +714,7 @@ int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *u
     // stack.  The fast discipline keeps every pending sibling as its own LDS entry (fewest VALU instructions in a
     // VALU-issue-bound kernel) and gets the entries that still allow 5 workgroups per CU next to the 4 KB output
     // staging: 27 (measured: <= 31 KiB of LDS per workgroup -> 5 resident, 32 KiB -> 4); rays of the 3601^2 tile use
-    // <= 20.  Its worst case (3 per level) does not fit, so an overflowing wave raises counters[8] and horizon_run
+    // <= 20.  Its worst case (3 per level) does not fit, so an overflowing wave raises counters[HZ_CNT_OVERFLOW] and horizon_run
     // repeats that launch with the one-entry-per-level discipline (`height` entries, cannot overflow, +10 % VALU) and
     // keeps it for the scene.  Shallow trees whose worst case fits never need the second kernel.
     const int stage = ((a.azim_num & 3) == 0 && (reinterpret_cast<size_t>(a.hori) & 15) == 0) ? 4 * HZ_TPB * 4 : 0;
@@ -784,7 +784,7 @@ int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *u
     p.left_out_ctl = left_ctl + 16 * std::min(p.left_mode, HZ_LEFT_LEVELS - 1);
     // persistent waves (k_horizon): the default for full launches; a.no_persist restores one tile per workgroup (same-box A/Bs)
     p.persist = (a.tile_list == nullptr && ((!a.no_persist && HZ_WPB == 4) || p.left_mode)) ? 1 : 0;
-    p.queue = reinterpret_cast<unsigned *>(a.counters + 24);
+    p.queue = reinterpret_cast<unsigned *>(a.counters + HZ_CNT_QUEUES);
     const size_t lds = (size_t)p.pre_bytes + (size_t)p.stack_bytes + (size_t)top * sizeof(Node);
     const int grid = a.tile_list ? (a.n_list + HZ_WPB - 1) / HZ_WPB : p.tm.per_xcd * 8 * (4 / HZ_WPB);
     if (grid <= 0) return HZ_OK;

@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include "../../include/horayzon_hip.h"
 #include "hz_common.h"
+#include "hz_horizon_plan.h"
 #include <atomic>
 #include <mutex>
 
@@ -74,12 +76,21 @@ struct Scene {
     // (`const hz_scene *`, ctypes releases the GIL) and simply run one after the other -- they share the stream, so
     // the GPU would serialise them anyway.  This is what makes the scene-owned scratch below safe.
     mutable std::mutex run_mu;
-    // scratch of the near-field certificates, grown on demand and kept with the scene (hz_api.hip; guarded by run_mu)
+    // scratch of the near-field certificates, grown on demand and kept with the scene (hz_api_horizon.hip; guarded by run_mu)
     mutable void *near_buf = nullptr;
     mutable size_t near_bytes = 0;
     // records of the cells a production launch of k_horizon left unfinished (hz_horizon.hip: leftover cells; guarded by run_mu)
     mutable void *left_buf = nullptr;
     mutable size_t left_bytes = 0;
+    // grows one of the two scratch buffers to `need` bytes (the old contents are dropped); false: hipMalloc failed, the buffer is empty
+    static bool grow_scratch(void *&buf, size_t &bytes, size_t need) {
+        if (bytes >= need) return true;
+        if (buf) (void)hipFree(buf);
+        buf = nullptr; bytes = 0;
+        if (hipMalloc(&buf, need) != hipSuccess) { (void)hipGetLastError(); buf = nullptr; return false; }
+        bytes = need;
+        return true;
+    }
     BlobHeader hdr;
     const float *verts() const { return (const float *)((const char *)blob + hdr.off_verts); }
     const Node *nodes() const { return (const Node *)((const char *)blob + hdr.off_nodes); }
@@ -133,8 +144,52 @@ inline TileMap make_tile_map(int tiles_i, int tiles_j, int gw = 8) {
 // true if p points to device memory (HBM); false for host memory
 bool is_device_ptr(const void *p);
 
+// device view of an input array that may live on the host
+template <typename T>
+struct DevIn {
+    const T *dev = nullptr;
+    void *owned = nullptr;
+    ~DevIn() { if (owned) (void)hipFree(owned); }
+    int bind(const T *src, size_t count, hipStream_t st) {
+        if (!src || count == 0) { dev = nullptr; return HZ_OK; }
+        if (is_device_ptr(src)) { dev = src; return HZ_OK; }
+        HZ_HIP(hipMalloc(&owned, count * sizeof(T)));
+        HZ_HIP(hipMemcpyAsync(owned, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+        dev = static_cast<const T *>(owned);
+        return HZ_OK;
+    }
+};
+
+// device buffer for an output array that may live on the host
+template <typename T>
+struct DevOut {
+    T *dev = nullptr;
+    T *host = nullptr;
+    void *owned = nullptr;
+    size_t count = 0;
+    ~DevOut() { if (owned) (void)hipFree(owned); }
+    int bind(T *dst, size_t n) {
+        count = n;
+        if (!dst || n == 0) { dev = nullptr; return HZ_OK; }
+        if (is_device_ptr(dst)) { dev = dst; return HZ_OK; }
+        HZ_HIP(hipMalloc(&owned, n * sizeof(T)));
+        dev = static_cast<T *>(owned); host = dst;
+        return HZ_OK;
+    }
+    int finish(hipStream_t st) {
+        if (host && count) HZ_HIP(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, st));
+        return HZ_OK;
+    }
+};
+
+// streams come from a per-device pool and go back to it: the library never calls hipStreamDestroy (hz_api.hip)
+int stream_acquire(int device, hipStream_t *st);
+void stream_release(int device, hipStream_t st);
+
+// horizon_comp.cpp:37-39
+inline float deg2rad_f(float ang) { return (float)(((double)ang / 180.0) * M_PI); }
+
 // hz_horizon.hip
-#define HZ_LEFT_LEVELS 4                 // leftover regions (hand-over levels)
 struct HorizonArgs {
     const float *vec_norm, *vec_north;   // device
     const uint8_t *mask;                 // device
@@ -167,26 +222,33 @@ struct HorizonArgs {
     unsigned left_cap_max = 0;
     int no_persist = 0;                  // 1: one tile per workgroup instead of persistent waves (same-box A/Bs, tests)
     int persist_grid = 0;                // > 0 (tests): that many workgroups in a persistent launch, so that small grids run the block loop
-    unsigned long long *counters;        // device u64[HZ_CNT_N] + int[HZ_REDO_CAP] (tiles to redo, count in [8]): [0] rays, [1] guards, [2] nodes, [3] tris, [4] cells,
-                                         // [5..7] wave iterations, [8] waves whose fast-discipline stack overflowed,
-                                         // [9] rays shortened by a certificate, [10] certificate violations (verify), [11] cells with a guard event,
-                                         // [21] shortened rays that were re-traced (verify);
-                                         // [22] leaf tests done by a partner lane, [23] leaf-step lanes with a second leaf and no helper (leaf lending, counting instantiation);
-                                         // [24..27] = unsigned[8]: the per-XCD block queues of a persistent launch (hz_horizon.hip; zeroed by horizon_launch);
-                                         // [HZ_CNT_LEFT ..): unsigned[HZ_LEFT_LEVELS][16], the control words of the leftover regions: [r][0] = slots
-                                         // allocated in region r, [r][1] = valid records (k_left_keys), [r][8 + x] = groups of 64 handed to XCD x
+    unsigned long long *counters;        // device u64[HZ_CNT_N] (the words: HZ_CNT_* below) + 2 x int[HZ_REDO_CAP] (blocks / groups to redo)
 };
-// default hand-over thresholds: byte l = level l (hz_opts.left_min)
-#define HZ_LEFT_DEFAULT 0x00000024u
+// the u64 words of HorizonArgs::counters (k_horizon adds to them; horizon_run zeroes them per chunk and reads them back)
+enum {
+    HZ_CNT_RAYS = 0, HZ_CNT_GUARDS = 1, HZ_CNT_NODES = 2, HZ_CNT_TRIS = 3, HZ_CNT_CELLS = 4,
+    HZ_CNT_WAVE_NODE = 5, HZ_CNT_WAVE_LEAF = 6, HZ_CNT_WAVE_REFILL = 7,     // wave-level node / leaf / refill iterations
+    HZ_CNT_OVERFLOW = 8,                 // 8 x 8 blocks whose fast-discipline stack overflowed (they are in the first redo list)
+    HZ_CNT_SHORTENED = 9,                // rays shortened by a certificate
+    HZ_CNT_VIOLATIONS = 10,              // certificate violations (verify)
+    HZ_CNT_GUARD_CELLS = 11,             // cells with a guard event
+    HZ_CNT_XCD_END = 12,                 // [12..19] counting instantiation: when the last wave of XCD x finished ...
+    HZ_CNT_START = 20,                   // ... and ~(the earliest start)
+    HZ_CNT_VERIFIED = 21,                // shortened rays that were re-traced (verify)
+    HZ_CNT_LENT = 22, HZ_CNT_UNHELPED = 23,    // leaf lending, counting instantiation: leaf tests done by a partner lane, leaf-step lanes with a second leaf and no helper
+    HZ_CNT_QUEUES = 24,                  // [24..27] = unsigned[8]: the per-XCD block queues of a persistent launch (zeroed by horizon_launch)
+    HZ_CNT_LEFT_CELLS = 28, HZ_CNT_LEFT_AGAIN = 29,    // cells handed over by the production launch / again by a follow-up launch
+    HZ_CNT_LEFT_OVERFLOW = 30            // groups of the follow-up launch whose fast stack overflowed (the second redo list)
+};
 // follow-up launches (hz_opts.left_tune; swept in round 6, profiles/r06/ab_leftover_tune.log: 73 ms against 76 with classes of one
 // azimuth and the production launch's threshold of 36; classes of 32 azimuths: 95 ms)
 #define HZ_LEFT_KEY_SHIFT 3              // log2 of the width of the azimuths-left classes of the sort key: 8 azimuths
 #define HZ_LEFT_REGROUP 24               // compaction threshold in lanes under rule 0 of hz_n_leave (the absolute threshold) ...
 #define HZ_LEFT_REGROUP_REL 32           // ... and under rule 1 (profiles/r09/ab_regroup_rule.log: follow-up launch 73.0 -> 71.1 ms, 40 and 48 tie, 56 loses)
-#define HZ_CNT_LEFT 32                   // first u64 word of the leftover control words
+#define HZ_CNT_LEFT 32                   // [32..63] = unsigned[HZ_LEFT_LEVELS][16], the control words of the leftover regions: [r][0] = slots
+                                         // allocated in region r, [r][1] = valid records (k_left_keys), [r][8 + x] = groups of 64 handed to XCD x
 #define HZ_CNT_REFILL 64                 // counting instantiation: [64..71] refills by lanes served (8 buckets of 8), [72..79] by lanes entering hz_trace behind them
 #define HZ_CNT_N 80                      // u64 words in front of the redo list
-#define HZ_LEFT_WORDS 16                 // 32-bit words per leftover record
 #define HZ_REDO_CAP 16384                // 8 x 8 blocks of one launch that can be repeated one by one after a stack overflow
 int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *used_level_stack = nullptr);
 int left_sort(const HorizonArgs &a, int region, hipStream_t st);

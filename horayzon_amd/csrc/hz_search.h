@@ -2,7 +2,7 @@
 // state machine (ray_discrete_sampling / ray_binary_search / ray_guess_const,
 // horizon_comp.cpp:302-498, and the *_hori_dist variants :519-612).  Shared by the gridded
 // and the locations kernels.  The float/double promotion pattern of the reference's index
-// arithmetic is reproduced exactly; tables are built on the host (hz_api.hip) and only read here.
+// arithmetic is reproduced exactly; tables are built on the host (hz_api_horizon.hip) and only read here.
 #pragma once
 #include "hz_internal.h"
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ float half_sum(float a, float b) {
 
 // index of the table entry nearest to the midpoint of entries `a` and `b` (horizon_comp.cpp:462-464,
 // :490-492).  The search steps by 10 entries, so the midpoint index comes from a host-built table
-// (same float/double expressions, hz_api.hip); clamped steps at the table ends take the general path.
+// (same float/double expressions, hz_api_horizon.hip); clamped steps at the table ends take the general path.
 // *ev = elev_ang[that index], the value the search emits: the table holds (index, value bits) pairs -- one 8 B load.
 __device__ __forceinline__ int mid_index(const Tables &t, int a, int b, float *ev) {
     const int lo = min(a, b);

@@ -10,9 +10,12 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 obj=/tmp/hz_variant_$name
 mkdir -p $obj
 cd $R/horayzon_amd/csrc
-for f in hz_api hz_scene hz_horizon hz_shadow hz_locations hz_prep hz_sort hz_bench hz_near; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-result $flags -c $f.hip -o $obj/$f.o &
+srcs=$(make -s print-srcs)      # the Makefile's SRCS: one list of sources
+objs=
+for f in $srcs; do
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-result $flags -c $f -o $obj/${f%.hip}.o &
+  objs="$objs $obj/${f%.hip}.o"
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/horayzon_amd/libhorayzon_hip_$name.so $obj/*.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/horayzon_amd/libhorayzon_hip_$name.so $objs
 echo built horayzon_amd/libhorayzon_hip_$name.so
