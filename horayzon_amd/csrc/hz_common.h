@@ -406,10 +406,19 @@ __device__ __forceinline__ void hz_node_hits(const NodeRay &n, const RayBox &r, 
 // instructions (v_cmp_le_f32 4.2 cycles, v_cndmask_b32 with a scalar mask 4.1: profiles/r04/inst_rates.json), a fused
 // multiply-add, an arithmetic shift and a logic operation fast-class ones (2.3 - 2.5).  One rounding instead of two, and a
 // box whose interval has shrunk to exactly a point (tmin == tmax * slack) now counts as missed: both are far inside the slack.
-__device__ __forceinline__ void hz_node_hit_masks(const NodeRay &n, const RayBox &r, float tfar, const uint4 &q,
-                                                  int &m0, int &m1, int &m2, int &m3) {
-    const uint32_t px0 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.x, r.sel_x), px1 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.x, r.sel_x + HZ_SEL_PAIR1);
-    const uint32_t py0 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.y, r.sel_y), py1 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.y, r.sel_y + HZ_SEL_PAIR1);
+// LEAN (hz_trace<..., LEAN>): what the compiler re-forms in every node step when it has no register to keep it is handed in by the
+// caller, who forms it once per call -- sel_x1 / sel_y1 = the pair-1 selectors of x and y -- and min(., tfar) reads tfar from its scalar
+// register (hz_min_uniform: no canonical copy of a value that is never a NaN).
+__device__ __forceinline__ float hz_min_uniform(float a, float uniform_b) {
+    float r;
+    asm("v_min_f32_e32 %0, %2, %1" : "=v"(r) : "v"(a), "s"(uniform_b));
+    return r;
+}
+template <bool LEAN>
+__device__ __forceinline__ void hz_node_hit_masks_t(const NodeRay &n, const RayBox &r, uint32_t sel_x1, uint32_t sel_y1, float tfar, const uint4 &q,
+                                                    int &m0, int &m1, int &m2, int &m3) {
+    const uint32_t px0 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.x, r.sel_x), px1 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.x, sel_x1);
+    const uint32_t py0 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.y, r.sel_y), py1 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.y, sel_y1);
     const uint32_t pz0 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.z, r.sel_z), pz1 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.z, r.sel_z + HZ_SEL_PAIR1);
     const uint32_t pz2 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.w, r.sel_z), pz3 = __builtin_amdgcn_perm(HZ_HALF_MAGIC, q.w, r.sel_z + HZ_SEL_PAIR1);
     const float nx0 = hz_fma_mix_lo(px0, n.ax, n.bx), fx0 = hz_fma_mix_hi(px0, n.ax, n.bx);
@@ -417,7 +426,7 @@ __device__ __forceinline__ void hz_node_hit_masks(const NodeRay &n, const RayBox
     const float ny0 = hz_fma_mix_lo(py0, n.ay, n.by), fy0 = hz_fma_mix_hi(py0, n.ay, n.by);
     const float ny1 = hz_fma_mix_lo(py1, n.ay, n.by), fy1 = hz_fma_mix_hi(py1, n.ay, n.by);
     const float cx0 = __builtin_fmaxf(nx0, 0.0f), cx1 = __builtin_fmaxf(nx1, 0.0f);
-    const float gx0 = __builtin_fminf(fx0, tfar), gx1 = __builtin_fminf(fx1, tfar);
+    const float gx0 = LEAN ? hz_min_uniform(fx0, tfar) : __builtin_fminf(fx0, tfar), gx1 = LEAN ? hz_min_uniform(fx1, tfar) : __builtin_fminf(fx1, tfar);
 #define HZ_CHILD_M(pz, nx, fx, ny, fy, out) do { \
         const float nz_ = hz_fma_mix_lo(pz, n.az, n.bz), fz_ = hz_fma_mix_hi(pz, n.az, n.bz); \
         const float tmin_ = __builtin_fmaxf(__builtin_fmaxf(nx, ny), nz_); \
@@ -430,6 +439,10 @@ __device__ __forceinline__ void hz_node_hit_masks(const NodeRay &n, const RayBox
     HZ_CHILD_M(pz2, cx0, gx0, ny1, fy1, m2);
     HZ_CHILD_M(pz3, cx1, gx1, ny1, fy1, m3);
 #undef HZ_CHILD_M
+}
+__device__ __forceinline__ void hz_node_hit_masks(const NodeRay &n, const RayBox &r, float tfar, const uint4 &q,
+                                                  int &m0, int &m1, int &m2, int &m3) {
+    hz_node_hit_masks_t<false>(n, r, r.sel_x + HZ_SEL_PAIR1, r.sel_y + HZ_SEL_PAIR1, tfar, q, m0, m1, m2, m3);
 }
 
 // One 32 B node = 2 x 16 B global loads issued back to back and waited for once.
@@ -512,6 +525,21 @@ inline int hz_n_leave(int regroup, int n_entry, int rule, int round) {
     const int cut = cap < rel ? cap : rel;
     return cut > 1 ? cut : 1;
 }
+// The same with the two selects taken once per block instead of once per call (hz_trace<..., LEAN>): cap | share << 8 | round << 16.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int hz_n_leave_pack(int regroup, int rule, int round) {
+    return (rule ? 64 : regroup) | ((rule ? regroup : 64) << 8) | (round << 16);
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int hz_n_leave_packed(int pack, int n_entry) {
+    const int cap = pack & 0xff, rel = (((pack >> 8) & 0xff) * n_entry + (pack >> 16)) >> 6;
+    const int cut = cap < rel ? cap : rel;
+    return cut > 1 ? cut : 1;
+}
 
 #ifdef __HIPCC__
 struct LendCounters { unsigned lent, unhelped; };     // COUNT && LEND: leaf tests done by a partner lane; leaf-step lanes with a second leaf and no helper
@@ -519,6 +547,17 @@ struct TravState { int node, sp, pf, pm, lq0, lq1; };
 
 __device__ __forceinline__ void hz_trav_reset(TravState &t) {
     t.node = 0; t.sp = 0; t.pf = 0; t.pm = 0; t.lq0 = HZ_EMPTY; t.lq1 = HZ_EMPTY;
+}
+__device__ __forceinline__ void hz_lds_store(unsigned lds_byte_address, int v) {
+    *reinterpret_cast<__attribute__((address_space(3))) int *>((size_t)lds_byte_address) = v;
+}
+// hz_trace<..., LEAN>: the value of TravState::sp for a lane with `sp` entries above the sentinel -- the LDS byte address of the
+// entry below its top entry (`sa` in hz_trace)
+template <int TPB>
+__device__ __forceinline__ int hz_trav_sa(const int *stack, int tid, int sp) {
+    const unsigned sa0 = (unsigned)(size_t)reinterpret_cast<__attribute__((address_space(3))) int *>(
+                             (__attribute__((address_space(3))) char *)reinterpret_cast<char *>(const_cast<int *>(stack))) + (unsigned)tid * 4u;
+    return (int)(sa0 + (unsigned)(sp - 1) * (unsigned)(TPB * 4));
 }
 
 // (pf, pm) <-> one LDS word
@@ -543,7 +582,12 @@ __device__ __forceinline__ void hz_entry_unpack(int e, int &pf, int &pm) {
 // LEND (fast stack only): in a leaf step a lane without a leaf tests the SECOND queued leaf of its DPP partner (lane ^ 1, the
 //   neighbouring cell of the 8 x 8 block), see the leaf step below.  Any-hit: the decisions -- and the leaf that blocks -- are
 //   those of the plain schedule.
-template <int TPB, bool COUNT, int QLEN = 2, bool NODELET = false, bool LEVELSTACK = true, bool LEND = false>
+// LEAN (fast stack only; k_horizon's flat instantiations): what the stretch between two calls paid for on every exit and entry is
+//   done once by the caller.  t.sp holds the LDS byte address `sa` itself (hz_trav_sa: no division on the way out, no multiply on
+//   the way in), the caller stores the sentinel once per block (nothing ever overwrites entry 0), `regroup` is hz_n_leave_pack's
+//   word (regroup_rule is not read), the node's address is formed from the zero-extended link (a node link is never negative: no
+//   sign-extending shift), and the x and y pair-1 selectors are formed once per call (hz_node_hit_masks_t<true>).
+template <int TPB, bool COUNT, int QLEN = 2, bool NODELET = false, bool LEVELSTACK = true, bool LEND = false, bool LEAN = false>
 __device__ __forceinline__ int hz_trace(const Node *__restrict__ nodes, const Prim *__restrict__ prims,
                                         const float4 *top, int ntop, int *stack, int tid,
                                         float ox, float oy, float oz, float dx, float dy, float dz, float tfar,
@@ -579,22 +623,26 @@ __device__ __forceinline__ int hz_trace(const Node *__restrict__ nodes, const Pr
 //   * `overflow` is a lane mask in scalar registers (what the caller needs is "any lane of the wave").
 typedef __attribute__((address_space(3))) int hz_lds_int;
 #define HZ_STACK_AT(addr) (*reinterpret_cast<hz_lds_int *>((size_t)(addr)))
-#define HZ_SAVE() do { if (!LEVELSTACK) sp = (int)(sa - sa0) / (TPB * 4) + 1; \
+#define HZ_SAVE() do { if (!LEVELSTACK) sp = LEAN ? (int)sa : (int)(sa - sa0) / (TPB * 4) + 1; \
                        t.node = node; t.sp = sp; t.pf = pf; t.pm = pm; t.lq0 = lq0; t.lq1 = lq1; } while (0)
     const unsigned sa0 = (unsigned)(size_t)reinterpret_cast<hz_lds_int *>(
                              (__attribute__((address_space(3))) char *)reinterpret_cast<char *>(stack)) + (unsigned)tid * 4u;
-    unsigned sa = sa0 + (unsigned)(sp - 1) * (unsigned)(TPB * 4);
+    static_assert(!LEAN || !LEVELSTACK, "LEAN is a form of the fast stack");
+    unsigned sa = LEAN ? (unsigned)sp : sa0 + (unsigned)(sp - 1) * (unsigned)(TPB * 4);
     const unsigned sa_cap = sa0 + (unsigned)(stack_cap - 5) * (unsigned)(TPB * 4);
-    if (!LEVELSTACK) HZ_STACK_AT(sa0) = HZ_EMPTY;
+    if (!LEVELSTACK && !LEAN) HZ_STACK_AT(sa0) = HZ_EMPTY;
     unsigned sa_hi = 0u;          // highest stack pointer a NODE STEP of this call started with (overflow is decided once, at the
                                   // exit; a lane may enter with more: leaf links above the three free entries are fine)
     // The loop is left by the WAVE: when fewer than n_leave lanes are still traversing (`regroup`, and only if some lane
     // finished its ray in this call -- it can refill, so the caller always makes progress) or when none is.  A lane whose
     // ray is decided idles until then: a miss holds HZ_EMPTY and an empty queue; a hit holds HZ_EMPTY and the NUMBER of
     // the blocking leaf instead of its link in lq0 (non-negative: "no leaf queued"; never HZ_EMPTY).  No per-lane exit, no result register in the loop.
-    const int n_leave = hz_n_leave(regroup, n_entry, regroup_rule & 1, regroup_rule >> 1);      // (wave uniform: scalar registers)
+    const int n_leave = LEAN ? hz_n_leave_packed(regroup, n_entry)
+                             : hz_n_leave(regroup, n_entry, regroup_rule & 1, regroup_rule >> 1);      // (wave uniform: scalar registers)
     // The loop is rotated by hand: [queue fills + votes] once in front of it and again at the end of its body, so that the
     // wave's exit test is the loop condition itself.
+    uint32_t sel_x1 = rb.sel_x + HZ_SEL_PAIR1, sel_y1 = rb.sel_y + HZ_SEL_PAIR1;
+    if (LEAN) asm volatile("" : "+v"(sel_x1), "+v"(sel_y1));      // (or every node step forms them again)
     bool can_node, can_leaf;
     unsigned long long m_node, m_leaf;
     int n_all;
@@ -645,6 +693,7 @@ typedef __attribute__((address_space(3))) int hz_lds_int;
                 // a per-lane pointer select would be compiled into slow flat loads).  Measured 2 % slower
                 // than plain global loads -- the top of the tree is L1 resident -- so it is opt-in.
                 if (NODELET && node < ntop) hz_load_node_lds(top + 2 * node, n0, n1);
+                else if (LEAN) hz_load_node(nodes + (unsigned)node, n0, n1);      // (no sign extension; v_lshl_add_u64 shifts by 4 at most: two instructions)
                 else hz_load_node(nodes + node, n0, n1);
                 if (COUNT) { cnt.nodes++; HZ_WAVE_TICK(cnt.w_nodes, lane); }
                 const NodeRay nr = hz_node_ray(rb, n0.x, n0.y, n0.z);
@@ -665,7 +714,8 @@ typedef __attribute__((address_space(3))) int hz_lds_int;
                     HZ_POP();                        // ... and the first of them (or of a level above) is entered
                 } else {
                     int m0, m1, m2, m3;              // lane masks: all ones = child hit (hz_node_hit_masks)
-                    hz_node_hit_masks(nr, rb, tfar_box, n1, m0, m1, m2, m3);
+                    if (LEAN) hz_node_hit_masks_t<true>(nr, rb, sel_x1, sel_y1, tfar_box, n1, m0, m1, m2, m3);
+                    else hz_node_hit_masks(nr, rb, tfar_box, n1, m0, m1, m2, m3);
                     // out of entries: remember the highest pointer (checked once, at the exit) and clamp
                     sa_hi = max(sa_hi, sa);
                     sa = min(sa, sa_cap);

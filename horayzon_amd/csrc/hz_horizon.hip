@@ -30,6 +30,7 @@
 // reproduced exactly (hard part 2); tables are built on the
 // host with the reference's expressions (hz_api_horizon.hip) and only read here.
 #include "hz_search.h"
+#include <type_traits>
 #include <vector>
 
 namespace hz {
@@ -110,6 +111,9 @@ __device__ __forceinline__ void hz_left_write(unsigned *w, unsigned cert, unsign
 // (hz_debug_set("leaf_lend", 0 | 1), default 1): the instantiation without it is the same-library A/B and the tests' reference.
 // FLAT: the refill of guess_constant as one branch-free pass (advance_guess_flat, hz_search.h) instead of the state machine's if-chain.
 // Chosen at launch like LEND (hz_debug_set("flat_refill", 0 | 1), default 1), for the instantiations that have LEND.
+// The FLAT instantiations hold the lean search state (SearchLean, hz_search.h: azimuth 0's two limits live in LDS, `lim` below) and
+// call hz_trace<..., LEAN> (hz_common.h); every other instantiation keeps Search, advance<ALG> and the plain hz_trace.  A leftover
+// record is the same 16 words in both forms, and either form restores what the other wrote.
 template <int ALG, bool COUNT, bool STAGE, bool NODELET, bool LEVELSTACK, bool LEFT = false, bool LEND = false, bool FLAT = false>
 #ifndef HZ_WG_PER_CU
 #define HZ_WG_PER_CU 5     // resident workgroups per CU the register allocation is held to (6: 80 VGPRs, measured slower)
@@ -159,16 +163,29 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     // (the same for what is derived from the thread number -- lane, lane >> 3, lane & 7, LDS addresses: formed again in every pass
     //  from a copy the compiler cannot see through, or they are hoisted out of the block loop and live through the traversal)
     int tid_b = tid;
+    if (FLAT) {
+        // (and the copy itself from the wave's number and the lane's: the thread number no longer lives through the block -- it had no
+        //  register there and was spilled)
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        tid_b = (wave << 6) | (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero));
+    }
     asm volatile("" : "+v"(tid_b));
     const int lane = tid_b & 63;
     // (what the traversal loop and the refill read stays in registers: the compiler would otherwise re-load these from the
     //  argument segment INSIDE those loops -- an s_load and its wait in front of every vote)
 #define HZ_KEEP(x) asm volatile("" : "+s"(x))
+    // (FLAT: the threshold's constants in the form hz_trace<..., LEAN> reads, made here once per block)
+    if (FLAT) p.regroup = hz_n_leave_pack(p.regroup & 0xff, (p.regroup >> 8) & 1, p.regroup >> 9);
     HZ_KEEP(p.leaf_bias); HZ_KEEP(p.regroup); HZ_KEEP(p.neg_tau); HZ_KEEP(p.sv.cx); HZ_KEEP(p.sv.cy); HZ_KEEP(p.sv.cz);
     HZ_KEEP(p.near_idx); HZ_KEEP(p.near_r);
     // (the flat follow-up instantiation: without these the node and the leaf step each re-load the scene's pointers from the argument segment)
     if (FLAT && LEFT) { HZ_KEEP(p.sv.nodes); HZ_KEEP(p.sv.prims); }
 #undef HZ_KEEP
+    // (FLAT: the asm above hides from the compiler that the two certificate arrays are global memory; said again here, or their loads
+    //  are flat loads, which count on lgkmcnt too -- the ray set-up then waits for them where it waits for the LDS)
+    typedef const __attribute__((address_space(1))) unsigned short *hz_gl_u16;
+    typedef const __attribute__((address_space(1))) float *hz_gl_f32;
     int ti = 0, tj = 0;
     int blk = (int)blockIdx.x * HZ_WPB + wave;
     unsigned rec0 = 0u, rec_n = 0u;                  // LEFT: first entry of the sorted permutation of this wave's group, entries in it
@@ -245,6 +262,12 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     out.dist = nullptr; out.dist_hit = 0.0f;
     out.stage = reinterpret_cast<float *>(smem) + tid_b;   // only touched when STAGE
     out.stride = HZ_TPB;
+    // FLAT: this lane's words of the two LDS rows directly below the stack, for lim_up / lim_low of azimuth 0 (SearchLean).  They are
+    // the last two rows of pre_bytes (horizon_launch: four rows with staging, two without): rows 2 and 3 of the staging buffer --
+    // row 3 is never staged, row 2 first at azimuth 2 -- or the two padding rows.  The stack reads them with its top, never uses them.
+    float *const lim = out.stage + (STAGE ? 2 : 0) * HZ_TPB;
+    static_assert(!FLAT || !LEVELSTACK, "the flat refill is built for the fast stack");
+    if (FLAT) stack[tid_b] = HZ_EMPTY;      // the fast stack's sentinel, entry 0: once per block (hz_trace<..., LEAN>)
     float ox = 0, oy = 0, oz = 0;
     float r01 = 0, r02 = 0, r11 = 0, r12 = 0, r21 = 0, r22 = 0;
     const bool masked = in_dom && p.mask[cell] != 1;
@@ -284,9 +307,9 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
         ocx = ax_ - p.sv.cx; ocy = ay_ - p.sv.cy; ocz = az_ - p.sv.cz; }
     const float tfar = p.dist;
 
-    Search s;
+    typename std::conditional<FLAT, SearchLean, Search>::type s;
     s.k = 0; s.phase = PH_NEWAZ; s.ind = 0; s.prev = 0; s.pazim = 0; s.count = 0;
-    s.lim_up = 0; s.lim_low = 0; s.elev_samp = 0; s.ev = 0;
+    if constexpr (!FLAT) { s.lim_up = 0; s.lim_low = 0; s.elev_samp = 0; s.ev = 0; }
     unsigned rays = 0, guards = 0, w_adv = 0;
     // COUNT: refills of this wave by population, tallied by the lane whose number is the bucket: lanes 0 - 7 by the lanes the
     // refill serves (1 - 8, 9 - 16, ...), lanes 8 - 15 by the lanes that enter hz_trace behind it (n_entry, same buckets)
@@ -297,7 +320,11 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     bool ray_active = false, last_hit = false;
     float dx = 0, dy = 0, dz = 1;
     RayBox rb = hz_raybox(0, 0, 0, 0, 0, 1);
-    TravState ts; hz_trav_reset(ts);
+    // (FLAT: ts.sp is the LDS byte address hz_trace<..., LEAN> works with; SP entries above the sentinel)
+    // (formed from a copy of the thread number the compiler cannot see through: hoisted out of the loops it was spilled)
+#define HZ_TS_RESET(SP) do { hz_trav_reset(ts); if (FLAT) { int tid_r = tid_b; asm volatile("" : "+v"(tid_r)); \
+                             ts.sp = hz_trav_sa<HZ_TPB>(stack, tid_r, (SP)); } else ts.sp = (SP); } while (0)
+    TravState ts; HZ_TS_RESET(0);
     int cache = 0;           // hit cache: subtree above the leaf that blocked this cell's last blocked ray
     bool second = false;     // the cache walk found nothing: the root traversal is still due
     bool overflow = false;   // !LEVELSTACK: a ray needed more stack entries than this launch has (see hz_trace)
@@ -316,11 +343,13 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
         // was in flight, issued again here from (s.ind, s.k) over its full length from the root (the decision cannot differ: no
         // certificate, no cache walk, section 4 of DESIGN.md); it was counted when it was issued first
         s.k = (int)rec[1]; s.phase = (int)(rec[2] & 0xffu); s.ind = (int)rec[3]; s.prev = (int)rec[4]; s.pazim = (int)rec[5]; s.count = (int)rec[6];
-        s.lim_up = __uint_as_float(rec[7]); s.lim_low = __uint_as_float(rec[8]); s.elev_samp = __uint_as_float(rec[9]); s.ev = __uint_as_float(rec[10]);
+        if constexpr (!FLAT) { s.lim_up = __uint_as_float(rec[7]); s.lim_low = __uint_as_float(rec[8]); s.elev_samp = __uint_as_float(rec[9]); s.ev = __uint_as_float(rec[10]); }
         cache = (int)rec[11];
         last_hit = (rec[2] & 0x100u) != 0u;
         had_guard = (rec[2] & 0x400u) != 0u;
         if (STAGE) { out.stage[0] = __uint_as_float(rec[12]); out.stage[out.stride] = __uint_as_float(rec[13]); out.stage[2 * out.stride] = __uint_as_float(rec[14]); }
+        // (behind the staged values: with staging lim[0] is row 2 of the staging buffer, which a cell in azimuth 0 has not staged into)
+        if (FLAT && s.phase == PH_BIN) { lim[0] = __uint_as_float(rec[7]); lim[HZ_TPB] = __uint_as_float(rec[8]); }
         if (rec[2] & 0x200u) {
             const float ec = t.elev_cos[s.ind], es = t.elev_sin[s.ind];
             const float rx = ec * t.azim_sin[s.k], ry = ec * t.azim_cos[s.k], rz = es;
@@ -330,7 +359,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
             dz = (r20 * rx + r21 * ry) + r22 * rz;
             HZ_OC(ocx, ocy, ocz)
             rb = hz_raybox(ocx + p.neg_tau * dx, ocy + p.neg_tau * dy, ocz + p.neg_tau * dz, dx, dy, dz);
-            hz_trav_reset(ts);
+            HZ_TS_RESET(0);
             ray_active = true;
         }
     }
@@ -358,8 +387,13 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
                     if (!done) {
                         const unsigned rank = (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(um >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)um, 0u));
                         const unsigned flags = (unsigned)s.phase | (last_hit ? 0x100u : 0u) | (ray_active ? 0x200u : 0u) | ((guards != 0u || had_guard) ? 0x400u : 0u);
+                        // (words 7 - 10.  FLAT: the two LDS words of a cell in azimuth 0's binary search, else zeros -- what the other
+                        //  form of the restore reads from a record in any other phase is never used)
+                        float w7 = 0.0f, w8 = 0.0f, w9 = 0.0f, w10 = 0.0f;
+                        if constexpr (FLAT) { if (s.phase == PH_BIN) { w7 = lim[0]; w8 = lim[HZ_TPB]; } }
+                        else { w7 = s.lim_up; w8 = s.lim_low; w9 = s.elev_samp; w10 = s.ev; }
                         hz_left_write(out_rec + (size_t)(base + rank) * HZ_LEFT_WORDS, cert, (unsigned)s.k, flags,
-                                      (unsigned)s.ind, (unsigned)s.prev, (unsigned)s.pazim, (unsigned)s.count, s.lim_up, s.lim_low, s.elev_samp, s.ev, (unsigned)cache,
+                                      (unsigned)s.ind, (unsigned)s.prev, (unsigned)s.pazim, (unsigned)s.count, w7, w8, w9, w10, (unsigned)cache,
                                       STAGE ? out.stage[0] : 0.0f, STAGE ? out.stage[out.stride] : 0.0f, STAGE ? out.stage[2 * out.stride] : 0.0f);
                         done = true;
                     }
@@ -395,7 +429,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
                 if (COUNT) want_v = (GO) && p.verify_near && tn > 0.0f && (((rays + cert) & p.verify_mask) == 0u); \
                 HZ_OC(ocx, ocy, ocz) \
                 rb = hz_raybox(ocx + tn * dx, ocy + tn * dy, ocz + tn * dz, dx, dy, dz); \
-                hz_trav_reset(ts); \
+                HZ_TS_RESET(0); \
                 /* a ray below the previous azimuth's horizon is expected to be blocked near the same ridge */ \
                 second = p.hit_cache && (cache != 0) && (s.ind <= s.pazim) && (s.k > 0); \
                 if (second) { \
@@ -406,21 +440,22 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
                        the level stack, whose entries cannot name the root), but the lane does not idle until its wave leaves. \
                        Depth: the walk below the cached node needs <= 3 * anc_levels entries above this one, far below the \
                        root traversal's own maximum, so no launch overflows that did not before. */ \
-                    if (!LEVELSTACK) { ts.sp = 1; stack[HZ_TPB + tid] = 0; second = false; } \
+                    if (FLAT) { ts.sp += HZ_TPB * 4; hz_lds_store((unsigned)ts.sp + (unsigned)(HZ_TPB * 4), 0); second = false; }      /* (entry 1 is one row above `sa`) */ \
+                    else if (!LEVELSTACK) { ts.sp = 1; stack[HZ_TPB + tid] = 0; second = false; } \
                 }
-            if (FLAT) {
+            if constexpr (FLAT) {
                 // the refill without a branch per search phase (hz_search.h): the azimuth's table entries and the certificate are
                 // asked for as soon as the next azimuth is known -- together with the midpoint pair --, the elevation's entries
                 // once that pair is there: two memory round trips.  Every lane of the refill runs the set-up; a lane whose cell
                 // is finished (GO false) computes a ray it never traces.
                 float ec = 0.0f, es = 0.0f, asn = 0.0f, acs = 0.0f, near_rad = 0.0f;
                 int near_i = 0x7fffffff;
-                const bool go = advance_guess_flat<STAGE>(s, last_hit, t, out, guards,
+                const bool go = advance_guess_flat<STAGE>(s, last_hit, t, out, guards, lim, HZ_TPB,
                     [&](int kc) {
                         asn = t.azim_sin[kc]; acs = t.azim_cos[kc];
                         if (p.near_idx != nullptr) {
-                            near_i = (int)p.near_idx[(size_t)cert_r * (size_t)t.azim_num + kc];
-                            near_rad = p.near_r[cert_r];
+                            near_i = (int)((hz_gl_u16)p.near_idx)[(size_t)cert_r * (size_t)t.azim_num + kc];
+                            near_rad = ((hz_gl_f32)p.near_r)[cert_r];
                         }
                     },
                     [&](int ind) { ec = t.elev_cos[ind]; es = t.elev_sin[ind]; });
@@ -458,16 +493,16 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
         }
         if (ray_active) {
             int r;
-            r = hz_trace<HZ_TPB, COUNT, HZ_QLEN, NODELET, LEVELSTACK, LEND>(p.sv.nodes, p.sv.prims, top, ntop, stack, tid, ox, oy, oz,
-                                                 dx, dy, dz, tfar, p.dist_box, rb, ts, p.regroup & 0xff, p.leaf_bias, tc, p.stack_cap, overflow, &lc, p.regroup >> 8);
+            r = hz_trace<HZ_TPB, COUNT, HZ_QLEN, NODELET, LEVELSTACK, LEND, FLAT>(p.sv.nodes, p.sv.prims, top, ntop, stack, FLAT ? tid_b : tid, ox, oy, oz,
+                                                 dx, dy, dz, tfar, p.dist_box, rb, ts, FLAT ? p.regroup : (p.regroup & 0xff), p.leaf_bias, tc, p.stack_cap, overflow, &lc, p.regroup >> 8);
             if (r == 0 && second) {                      // nothing in the cached subtree: full traversal
-                second = false; hz_trav_reset(ts);
+                second = false; HZ_TS_RESET(0);
             } else if (COUNT && want_v && r != 2) {
                 // the shortened ray is done: trace it again over its full length and compare the decisions
                 want_v = false; verifying = true; first_result = (r == 1); start_v = true;
                 HZ_OC(ocx, ocy, ocz)
                 rb = hz_raybox(ocx + p.neg_tau * dx, ocy + p.neg_tau * dy, ocz + p.neg_tau * dz, dx, dy, dz);
-                hz_trav_reset(ts);
+                HZ_TS_RESET(0);
             } else if (r != 2) {
                 if (COUNT && verifying) { viol = ((r == 1) != first_result); verifying = false; }
                 ray_active = false; last_hit = (r == 1);
@@ -534,6 +569,7 @@ __global__ __launch_bounds__(HZ_TPB, (COUNT ? 4 : HZ_WG_PER_CU) * (4 / HZ_WPB)) 
     }   // (!wave_overflowed)
     if (!p.persist) break;
   }     // next block of this wave
+#undef HZ_TS_RESET
 }
 
 std::atomic<int> g_leaf_lend{1};      // hz_debug_set("leaf_lend", 0 | 1) (hz_internal.h)
@@ -718,7 +754,9 @@ int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *u
     // repeats that launch with the one-entry-per-level discipline (`height` entries, cannot overflow, +10 % VALU) and
     // keeps it for the scene.  Shallow trees whose worst case fits never need the second kernel.
     const int stage = ((a.azim_num & 3) == 0 && (reinterpret_cast<size_t>(a.hori) & 15) == 0) ? 4 * HZ_TPB * 4 : 0;
-    // (two rows: a lane that has popped its sentinel but still has queued leaves reads the two rows below the stack)
+    // (two rows: a lane that has popped its sentinel but still has queued leaves reads the two rows below the stack.  The FLAT
+    //  instantiations keep azimuth 0's two search limits in the last two rows of `pre` -- `lim` in k_horizon counts on exactly these
+    //  sizes: four rows with staging, two without)
     const int pre = stage ? stage : 2 * HZ_TPB * 4;
     const int height = std::max(sc->hdr.height, 1);
     // (a.level_stack < 0: test hook, the fast discipline with that many entries)

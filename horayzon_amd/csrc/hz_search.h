@@ -162,7 +162,49 @@ __device__ __forceinline__ bool advance(Search &s, bool hit, const Tables &t, Si
     }
 }
 
-// advance<ALG_GUESS, STAGE> as one pass without a loop (k_horizon<..., FLAT>): the same transitions on the same Search encoding.
+// The search state of the flat guess_constant refill (k_horizon<..., FLAT>): Search without the four floats that only the binary
+// search of azimuth 0 reads.  The two that persist from one ray to the next there, lim_up and lim_low, live in two LDS words of
+// the lane (lim[0], lim[lim_stride]: the two rows below the fast stack, k_horizon) while the lane is in PH_BIN; elev_samp and ev
+// never outlive the call that sets them.  Every other field means what it means in Search.
+struct SearchLean {
+    int k, phase, ind, prev, pazim, count;
+};
+
+// The transitions of advance<ALG_GUESS, STAGE> out of PH_NEWAZ and PH_BIN on a SearchLean: azimuth 0's binary search
+// (horizon_comp.cpp:398-428) up to the first sample of azimuth 1 (:439-446).  Same states, same emitted values.
+template <bool STAGE>
+__device__ __forceinline__ bool advance_az0_lean(SearchLean &s, bool hit, const Tables &t, Sink &out, float *lim, int lim_stride) {
+    const int top = t.elev_num - 1;
+    if (s.phase == PH_NEWAZ && s.k >= t.azim_num) return false;
+    if (s.phase == PH_BIN || s.k == 0) {
+        float lim_up = t.up, lim_low = t.low;
+        if (s.phase == PH_BIN) {                             // :417-424
+            const float e0 = t.elev_ang[s.ind];
+            lim_up = lim[0]; lim_low = lim[lim_stride];
+            if (hit) lim_low = e0; else lim_up = e0;
+        }
+        const float elev_samp = half_sum(lim_up, lim_low);
+        s.ind = ind_of(t, elev_samp);
+        s.phase = PH_BIN;
+        const float e = t.elev_ang[s.ind];
+        if (__builtin_fmaxf(lim_up - e, e - lim_low) > t.hori_acc) {
+            lim[0] = lim_up; lim[lim_stride] = lim_low;
+            return true;
+        }
+        s.pazim = s.ind;                                     // :428
+        emit<STAGE>(out, t, s.k, elev_samp);
+        s.k++; s.phase = PH_NEWAZ;
+        if (s.k >= t.azim_num) return false;
+    }
+    s.ind = max(s.pazim - 5, 0);                             // move upwards: :439-446
+    s.prev = s.ind;
+    s.ind = min(s.ind + 10, top);
+    s.count = 1;
+    s.phase = PH_UP;
+    return true;
+}
+
+// advance<ALG_GUESS, STAGE> as one pass without a loop (k_horizon<..., FLAT>): the same transitions on the Search encoding, held in a SearchLean.
 // After azimuth 0 a guess_constant lane is in PH_UP or PH_DOWN whenever a ray ends, and what happens next is one of
 //   step on    UP with a hit below the top index, DOWN with a miss above index 0
 //   turn round UP with a miss (or a hit at the top) on the first sample
@@ -177,13 +219,13 @@ __device__ __forceinline__ bool advance(Search &s, bool hit, const Tables &t, Si
 #define HZ_HIDE(m) asm volatile("" : "+v"(m))
 #define HZ_BSEL(m, x, y) (((m) & (x)) | (~(m) & (y)))
 template <bool STAGE, class FK, class FI>
-__device__ __forceinline__ bool advance_guess_flat(Search &s, bool hit, const Tables &t, Sink &out, unsigned &guards,
-                                                   FK &&issue_k, FI &&issue_ind) {
+__device__ __forceinline__ bool advance_guess_flat(SearchLean &s, bool hit, const Tables &t, Sink &out, unsigned &guards,
+                                                   float *lim, int lim_stride, FK &&issue_k, FI &&issue_ind) {
     const int top = t.elev_num - 1;
     int m_flat = (int)((unsigned)s.phase << 30) >> 31;       // PH_UP = 2, PH_DOWN = 3: bit 1
     HZ_HIDE(m_flat);
     if (__ballot(m_flat == 0) != 0ull) {                     // azimuth 0 only: no lane takes this after the first rays of a block
-        if (m_flat == 0) (void)advance<ALG_GUESS, STAGE>(s, hit, t, out, guards);      // (false: s.k == azim_num, see the return below)
+        if (m_flat == 0) (void)advance_az0_lean<STAGE>(s, hit, t, out, lim, lim_stride);      // (false: s.k == azim_num, see the return below)
     }
     // ---- decide ----  (every case mask is inside m_flat: the lanes of the branch above keep the state it left)
     int m_down = (int)((unsigned)s.phase << 31) >> 31;
@@ -222,7 +264,6 @@ __device__ __forceinline__ bool advance_guess_flat(Search &s, bool hit, const Ta
     s.phase += m_turn & 1;                                   // UP -> DOWN
     s.phase -= m_fin & m_down & 1;                           // DOWN -> UP (azimuth k + 1)
     s.pazim = HZ_BSEL(m_fin, mid, s.pazim);
-    s.ev = __int_as_float(HZ_BSEL(m_fin, evb, __float_as_int(s.ev)));
     s.k = k_new;
     if (m_fin != 0) emit<STAGE>(out, t, k_emit, __int_as_float(evb));      // one exec-mask region: the lanes that finalize
     return s.k < t.azim_num;
