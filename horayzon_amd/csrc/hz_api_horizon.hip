@@ -258,35 +258,6 @@ struct DevTables {
     }
 };
 
-// device memory that is freed with its scope
-struct DevBuf {
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-};
-
-// a timing event, created when it is first recorded
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-    int record(hipStream_t st) {
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return set_error(HZ_ERR_HIP, "hipEventCreate failed"); }
-        (void)hipEventRecord(e, st);
-        return HZ_OK;
-    }
-    // milliseconds from this event to `end`; 0 when one of them was never recorded
-    float ms_until(const Event &end) const {
-        float ms = 0.0f;
-        if (e && end.e) (void)hipEventElapsedTime(&ms, e, end.e);
-        return ms;
-    }
-};
-
 // Rows per launch and the device buffer of one chunk of horizon, when `hori` is host memory or skipped (SVF only).
 // Every launch ends with a tail (the last waves run on a draining GPU; a lane owns its cell for all azimuths), so launches
 // should be few: at least 16 GiB of horizon per launch when it is only the SVF's input (nothing is copied out; less if HBM is

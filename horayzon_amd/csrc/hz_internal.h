@@ -182,6 +182,39 @@ struct DevOut {
     }
 };
 
+// device memory that is freed with its scope
+struct DevBuf {
+    void *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+};
+
+// a timing event, created when it is first recorded
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    int record(hipStream_t st) {
+        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return set_error(HZ_ERR_HIP, "hipEventCreate failed"); }
+        (void)hipEventRecord(e, st);
+        return HZ_OK;
+    }
+    // milliseconds from this event to `end`; 0 when one of them was never recorded
+    float ms_until(const Event &end) const {
+        float ms = 0.0f;
+        if (e && end.e) (void)hipEventElapsedTime(&ms, e, end.e);
+        return ms;
+    }
+};
+
+// hz_api.hip: hipSetDevice after a range check; what hz_scene_destroy does (the sun-position drivers own scenes too)
+int select_device(int device);
+void scene_free(Scene *sc);
+
 // streams come from a per-device pool and go back to it: the library never calls hipStreamDestroy (hz_api.hip)
 int stream_acquire(int device, hipStream_t *st);
 void stream_release(int device, hipStream_t st);
@@ -303,8 +336,15 @@ struct ShadowArgs {
     uint8_t *out_u8; float *out_f32;
     int top_nodes;
     int count_work;                      // 1: the counting instantiation
-    unsigned long long *counters;        // device u64[16]: [0] rays; count_work: [1] node visits, [2] triangle tests,
-                                         // [3] / [4] wave-level node / leaf steps
+    unsigned long long *counters;        // device u64[HZ_SHADOW_CNT_N] (the words: HZ_SHADOW_CNT_* below)
+};
+// the u64 words of ShadowArgs::counters (the shadow kernels add to them; a Terrain call zeroes them and reads them back)
+enum {
+    HZ_SHADOW_CNT_RAYS = 0,
+    HZ_SHADOW_CNT_NODES = 1, HZ_SHADOW_CNT_TRIS = 2,               // count_work: node visits, triangle tests,
+    HZ_SHADOW_CNT_WAVE_NODE = 3, HZ_SHADOW_CNT_WAVE_LEAF = 4,      //   wave-level node / leaf steps
+    HZ_SHADOW_CNT_TWICE = 8,                                       // count_work: rays traced twice (the fast stack overflowed)
+    HZ_SHADOW_CNT_N = 16
 };
 int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st);
 int shadow_refrac_factor(const float *elevation, size_t n, double *out, hipStream_t st);

@@ -97,15 +97,15 @@ template <bool COUNT>
 __device__ __forceinline__ void shadow_counters(const ShadowParams &p, unsigned rays, const TravCounters &tc, int lane) {
     unsigned long long r = rays;
     for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off);
-    if (lane == 0 && r) atomicAdd(&p.counters[0], r);
+    if (lane == 0 && r) atomicAdd(&p.counters[HZ_SHADOW_CNT_RAYS], r);
     if (COUNT) {
         unsigned long long nc = tc.nodes, tn = tc.tris, wn = tc.w_nodes, wl = tc.w_leaves;
         for (int off = 32; off > 0; off >>= 1) {
             nc += __shfl_xor(nc, off); tn += __shfl_xor(tn, off); wn += __shfl_xor(wn, off); wl += __shfl_xor(wl, off);
         }
         if (lane == 0) {
-            atomicAdd(&p.counters[1], nc); atomicAdd(&p.counters[2], tn);
-            atomicAdd(&p.counters[3], wn); atomicAdd(&p.counters[4], wl);
+            atomicAdd(&p.counters[HZ_SHADOW_CNT_NODES], nc); atomicAdd(&p.counters[HZ_SHADOW_CNT_TRIS], tn);
+            atomicAdd(&p.counters[HZ_SHADOW_CNT_WAVE_NODE], wn); atomicAdd(&p.counters[HZ_SHADOW_CNT_WAVE_LEAF], wl);
         }
     }
 }
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SHADOW_WG) void k_shadow_ref
                 hz_trav_reset(ts);
                 res = hz_trace<HZ_TPB, COUNT, 2, false, true>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
                                                                     __builtin_inff(), __builtin_inff(), rb, ts, 0, HZ_SHADOW_LEAF_BIAS, tc, 0, unused);
-                if (COUNT && p.counters) atomicAdd(&p.counters[8], 1ull);     // rays traced twice
+                if (COUNT && p.counters) atomicAdd(&p.counters[HZ_SHADOW_CNT_TWICE], 1ull);     // rays traced twice
             }
             if (res != 2) {
                 shadow_result(p, cell, res == 1, r, out_u8, out_f32);
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SHADOW_WG) void k_accum_refi
                 hz_trav_reset(ts);
                 res = hz_trace<HZ_TPB, COUNT, 2, false, true>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
                                                                     __builtin_inff(), __builtin_inff(), rb, ts, 0, HZ_SHADOW_LEAF_BIAS, tc, 0, unused);
-                if (COUNT && p.counters) atomicAdd(&p.counters[8], 1ull);
+                if (COUNT && p.counters) atomicAdd(&p.counters[HZ_SHADOW_CNT_TWICE], 1ull);
             }
             if (res != 2) {
                 accum_result(ap, cell, res == 1, r, out_u8, out_f32);

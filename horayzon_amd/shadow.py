@@ -26,7 +26,73 @@ def _typed(a, dtype, ndim, name):
                          % (np.dtype(dtype).name, a.dtype.name))
 
 
+def _contiguous(a):
+    return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
+
+
+def _accumulate_types(obj, sun_positions, weights, outs):
+    """The argument types of ``accumulate``, in the order they are checked."""
+    obj._array_arg(sun_positions, 2, "sun_positions")
+    if weights is not None:
+        obj._array_arg(weights, 1, "weights")
+    for name, buf in outs:
+        if buf is not None:
+            obj._array_arg(buf, 2, name)
+
+
+def _accumulate_checks(sun_positions, weights, outs):
+    """The check list both ``accumulate`` methods share (``V.run``; HorizonTerrain appends its map checks)."""
+    given = [buf for _, buf in outs if buf is not None]
+    arrays = [sun_positions] + ([weights] if weights is not None else []) + given
+    return (
+        (ValueError, "at least one of 'sw_dir_cor_sum' and 'sunlit_sum' must be given", lambda: not given),
+        (ValueError, "array 'sun_positions' has incorrect shape",
+         lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
+        (ValueError, "array 'weights' has incorrect shape",
+         lambda: weights is not None and weights.shape[0] != sun_positions.shape[0]),
+        (ValueError, "not all input arrays are C-contiguous", lambda: not all(_contiguous(a) for a in arrays)),
+        (ValueError, "'sw_dir_cor_sum' and 'sunlit_sum' must be different arrays",
+         lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
+    )
+
+
+def _sw_dir_cor_coarse(obj, entry, sun_positions, pixel_per_gc, f_cor, sunlit_frac):
+    """``sw_dir_cor_coarse`` of both classes: the checks, then the entry point ``entry`` of the library."""
+    outs = (("f_cor", f_cor), ("sunlit_frac", sunlit_frac))
+    obj._array_arg(sun_positions, 2, "sun_positions")
+    p0, p1 = obj._pixel_per_gc(pixel_per_gc)
+    for name, buf in outs:
+        if buf is not None:
+            obj._array_arg(buf, 3, name)
+    if obj._shape is None:
+        raise _lib.HorayzonHipError("%s is not initialised" % obj._NAME)
+    given = [buf for _, buf in outs if buf is not None]
+    dim_0, dim_1 = obj._shape
+
+    def coarse_shape():
+        return (sun_positions.shape[0], dim_0 // p0, dim_1 // p1)
+    V.run((
+        (ValueError, "at least one of 'f_cor' and 'sunlit_frac' must be given", lambda: not given),
+        (ValueError, "array 'sun_positions' has incorrect shape",
+         lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
+        (ValueError, "'pixel_per_gc' (%d, %d) must be positive and divide the inner domain (%d, %d)" % (p0, p1, dim_0, dim_1),
+         lambda: p0 < 1 or p1 < 1 or p0 > dim_0 or p1 > dim_1 or dim_0 % p0 != 0 or dim_1 % p1 != 0),
+        (ValueError, "array 'f_cor' has incorrect shape",
+         lambda: f_cor is not None and tuple(f_cor.shape) != coarse_shape()),
+        (ValueError, "array 'sunlit_frac' has incorrect shape",
+         lambda: sunlit_frac is not None and tuple(sunlit_frac.shape) != coarse_shape()),
+        (ValueError, "not all input arrays are C-contiguous", lambda: not all(_contiguous(a) for a in [sun_positions] + given)),
+        (ValueError, "'f_cor' and 'sunlit_frac' must be different arrays",
+         lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
+    ))
+    st = hz_stats()
+    _lib.check(getattr(_lib.lib(), entry)(
+        obj._h, ptr(sun_positions), sun_positions.shape[0], p0, p1, ptr(f_cor), ptr(sunlit_frac), C.byref(st)))
+    obj.last_stats = st.as_dict()
+
+
 class Terrain:
+    _NAME = "Terrain"                   # in messages
 
     def __init__(self, *, device=0):
         self._h = C.c_void_p()
@@ -100,7 +166,7 @@ class Terrain:
 
     def _check_out(self, buf, name):
         if self._shape is None:
-            raise _lib.HorayzonHipError("Terrain is not initialised")
+            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
         if tuple(buf.shape[-2:]) != self._shape:
             raise ValueError("array '%s' has incorrect shape" % name)
 
@@ -186,20 +252,20 @@ class Terrain:
         self.last_stats = st.as_dict()
 
     # --- additive: weighted sums over many sun positions, no map per position -------------------------------------
-    def _accum_arg(self, buf, ndim, name):
-        """f32 argument of ``accumulate``: a NumPy array, or a torch tensor on the Terrain's GPU."""
+    def _array_arg(self, buf, ndim, name, np_dtype=np.float32, owner="Terrain"):
+        """Array argument of the additive calls: a NumPy array, or a torch tensor on the object's GPU."""
         if isinstance(buf, np.ndarray):
-            _typed(buf, np.float32, ndim, name)
+            _typed(buf, np_dtype, ndim, name)
             return
         if not hasattr(buf, "data_ptr"):
             raise TypeError("Argument '%s' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
                             % (name, type(buf).__name__))
         if buf.dim() != ndim:
             raise ValueError("Buffer has wrong number of dimensions (expected %d, got %d)" % (ndim, buf.dim()))
-        if str(buf.dtype).split(".")[-1] != "float32":
-            raise ValueError("Buffer dtype mismatch, expected 'float32' but got '%s'" % buf.dtype)
+        if str(buf.dtype).split(".")[-1] != np.dtype(np_dtype).name:
+            raise ValueError("Buffer dtype mismatch, expected '%s' but got '%s'" % (np.dtype(np_dtype).name, buf.dtype))
         if buf.device.type != "cuda" or buf.device.index != self.device:
-            raise ValueError("tensor '%s' is not on the Terrain's device (cuda:%d)" % (name, self.device))
+            raise ValueError("tensor '%s' is not on the %s's device (cuda:%d)" % (name, owner, self.device))
 
     def accumulate(self, sun_positions, weights=None, *, sw_dir_cor_sum=None, sunlit_sum=None):
         """Weighted sums over sun_positions f32[S][3] (S >= 1) without a map per position:
@@ -209,27 +275,8 @@ class Terrain:
         tensors on the Terrain's GPU; at least one.  Device memory besides the buffers does not grow with S
         (``last_stats["scratch_bytes"]``)."""
         outs = (("sw_dir_cor_sum", sw_dir_cor_sum), ("sunlit_sum", sunlit_sum))
-        self._accum_arg(sun_positions, 2, "sun_positions")
-        if weights is not None:
-            self._accum_arg(weights, 1, "weights")
-        for name, buf in outs:
-            if buf is not None:
-                self._accum_arg(buf, 2, name)
-        given = [buf for _, buf in outs if buf is not None]
-        arrays = [sun_positions] + ([weights] if weights is not None else []) + given
-
-        def contiguous(a):
-            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
-        V.run((
-            (ValueError, "at least one of 'sw_dir_cor_sum' and 'sunlit_sum' must be given", lambda: not given),
-            (ValueError, "array 'sun_positions' has incorrect shape",
-             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
-            (ValueError, "array 'weights' has incorrect shape",
-             lambda: weights is not None and weights.shape[0] != sun_positions.shape[0]),
-            (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in arrays)),
-            (ValueError, "'sw_dir_cor_sum' and 'sunlit_sum' must be different arrays",
-             lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
-        ))
+        _accumulate_types(self, sun_positions, weights, outs)
+        V.run(_accumulate_checks(sun_positions, weights, outs))
         for name, buf in outs:
             if buf is not None:
                 self._check_out(buf, name)
@@ -260,40 +307,7 @@ class Terrain:
         block's unmasked cells in row-major order, divided by their number in float64 and rounded to float32 once; a block
         without an unmasked cell gets ``sw_dir_cor_fill``.  Outputs f32[S][gy][gx], NumPy or torch tensors on the Terrain's
         GPU; at least one.  Device memory besides the outputs does not grow with S (``last_stats["scratch_bytes"]``)."""
-        outs = (("f_cor", f_cor), ("sunlit_frac", sunlit_frac))
-        self._accum_arg(sun_positions, 2, "sun_positions")
-        p0, p1 = self._pixel_per_gc(pixel_per_gc)
-        for name, buf in outs:
-            if buf is not None:
-                self._accum_arg(buf, 3, name)
-        if self._shape is None:
-            raise _lib.HorayzonHipError("Terrain is not initialised")
-        given = [buf for _, buf in outs if buf is not None]
-        dim_0, dim_1 = self._shape
-
-        def contiguous(a):
-            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
-
-        def coarse_shape():
-            return (sun_positions.shape[0], dim_0 // p0, dim_1 // p1)
-        V.run((
-            (ValueError, "at least one of 'f_cor' and 'sunlit_frac' must be given", lambda: not given),
-            (ValueError, "array 'sun_positions' has incorrect shape",
-             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
-            (ValueError, "'pixel_per_gc' (%d, %d) must be positive and divide the inner domain (%d, %d)" % (p0, p1, dim_0, dim_1),
-             lambda: p0 < 1 or p1 < 1 or p0 > dim_0 or p1 > dim_1 or dim_0 % p0 != 0 or dim_1 % p1 != 0),
-            (ValueError, "array 'f_cor' has incorrect shape",
-             lambda: f_cor is not None and tuple(f_cor.shape) != coarse_shape()),
-            (ValueError, "array 'sunlit_frac' has incorrect shape",
-             lambda: sunlit_frac is not None and tuple(sunlit_frac.shape) != coarse_shape()),
-            (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in [sun_positions] + given)),
-            (ValueError, "'f_cor' and 'sunlit_frac' must be different arrays",
-             lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
-        ))
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_sw_dir_cor_coarse(
-            self._h, ptr(sun_positions), sun_positions.shape[0], p0, p1, ptr(f_cor), ptr(sunlit_frac), C.byref(st)))
-        self.last_stats = st.as_dict()
+        _sw_dir_cor_coarse(self, "hz_terrain_sw_dir_cor_coarse", sun_positions, pixel_per_gc, f_cor, sunlit_frac)
 
 
 def _is_tensor(a):
@@ -316,6 +330,7 @@ class HorizonTerrain:
     are the method names and signatures.  Atmospheric refraction is switched on by ``refraction(elevation)`` after
     ``initialise`` (a method of its own: ``initialise`` keeps its arguments); every method then answers for the refracted
     sun, with ``Terrain``'s ``refrac_cor=True`` set-up word for word (clause 13)."""
+    _NAME = "HorizonTerrain"            # in messages
 
     def __init__(self, *, device=0):
         self._h = C.c_void_p()
@@ -479,13 +494,9 @@ class HorizonTerrain:
         return bool(getattr(self, "_refrac", False))
 
     _batch_out = staticmethod(Terrain._batch_out)
-    _accum_arg = Terrain._accum_arg
+    _array_arg = Terrain._array_arg
 
-    def _check_out(self, buf, name):
-        if self._shape is None:
-            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
-        if tuple(buf.shape[-2:]) != self._shape:
-            raise ValueError("array '%s' has incorrect shape" % name)
+    _check_out = Terrain._check_out
 
     def _run(self, sun_positions, weights, num_sun, **outs):
         st = hz_stats()
@@ -545,32 +556,14 @@ class HorizonTerrain:
         ``shadow_buffers`` u8[S][y][x] and ``sw_dir_cor_buffers`` f32[S][y][x] (keyword only, not in ``Terrain``; NumPy or
         torch/HBM) also take the per-position maps of the same pass."""
         outs = (("sw_dir_cor_sum", sw_dir_cor_sum), ("sunlit_sum", sunlit_sum))
-        self._accum_arg(sun_positions, 2, "sun_positions")
-        if weights is not None:
-            self._accum_arg(weights, 1, "weights")
-        for name, buf in outs:
-            if buf is not None:
-                self._accum_arg(buf, 2, name)
+        _accumulate_types(self, sun_positions, weights, outs)
         if shadow_buffers is not None:
             self._batch_out(shadow_buffers, np.uint8, "shadow_buffers")
         if sw_dir_cor_buffers is not None:
             self._batch_out(sw_dir_cor_buffers, np.float32, "sw_dir_cor_buffers")
         maps = [(n, b) for n, b in (("shadow_buffers", shadow_buffers), ("sw_dir_cor_buffers", sw_dir_cor_buffers))
                 if b is not None]
-        given = [buf for _, buf in outs if buf is not None]
-        arrays = [sun_positions] + ([weights] if weights is not None else []) + given
-
-        def contiguous(a):
-            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
-        V.run((
-            (ValueError, "at least one of 'sw_dir_cor_sum' and 'sunlit_sum' must be given", lambda: not given),
-            (ValueError, "array 'sun_positions' has incorrect shape",
-             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
-            (ValueError, "array 'weights' has incorrect shape",
-             lambda: weights is not None and weights.shape[0] != sun_positions.shape[0]),
-            (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in arrays)),
-            (ValueError, "'sw_dir_cor_sum' and 'sunlit_sum' must be different arrays",
-             lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
+        V.run(_accumulate_checks(sun_positions, weights, outs) + (
             (ValueError, "array 'shadow_buffers' / 'sw_dir_cor_buffers' has incorrect shape",
              lambda: any(b.shape[0] != sun_positions.shape[0] for _, b in maps)),
         ))
@@ -592,55 +585,7 @@ class HorizonTerrain:
         ``sw_dir_cor_fill``.  Outputs f32[S][gy][gx], NumPy or torch tensors on the object's GPU; at least one.  Both horizon
         layouts give the same words.  Device memory besides the outputs does not grow with S
         (``last_stats["scratch_bytes"]``)."""
-        outs = (("f_cor", f_cor), ("sunlit_frac", sunlit_frac))
-        self._accum_arg(sun_positions, 2, "sun_positions")
-        p0, p1 = self._pixel_per_gc(pixel_per_gc)
-        for name, buf in outs:
-            if buf is not None:
-                self._accum_arg(buf, 3, name)
-        if self._shape is None:
-            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
-        given = [buf for _, buf in outs if buf is not None]
-        dim_0, dim_1 = self._shape
-
-        def contiguous(a):
-            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
-
-        def coarse_shape():
-            return (sun_positions.shape[0], dim_0 // p0, dim_1 // p1)
-        V.run((
-            (ValueError, "at least one of 'f_cor' and 'sunlit_frac' must be given", lambda: not given),
-            (ValueError, "array 'sun_positions' has incorrect shape",
-             lambda: sun_positions.shape[1] != 3 or sun_positions.shape[0] < 1),
-            (ValueError, "'pixel_per_gc' (%d, %d) must be positive and divide the inner domain (%d, %d)" % (p0, p1, dim_0, dim_1),
-             lambda: p0 < 1 or p1 < 1 or p0 > dim_0 or p1 > dim_1 or dim_0 % p0 != 0 or dim_1 % p1 != 0),
-            (ValueError, "array 'f_cor' has incorrect shape",
-             lambda: f_cor is not None and tuple(f_cor.shape) != coarse_shape()),
-            (ValueError, "array 'sunlit_frac' has incorrect shape",
-             lambda: sunlit_frac is not None and tuple(sunlit_frac.shape) != coarse_shape()),
-            (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in [sun_positions] + given)),
-            (ValueError, "'f_cor' and 'sunlit_frac' must be different arrays",
-             lambda: len(given) == 2 and ptr(given[0]) == ptr(given[1])),
-        ))
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_horizon_terrain_sw_dir_cor_coarse(
-            self._h, ptr(sun_positions), sun_positions.shape[0], p0, p1, ptr(f_cor), ptr(sunlit_frac), C.byref(st)))
-        self.last_stats = st.as_dict()
-
-    def _sun_times_out(self, buf, np_dtype, name):
-        """Output map of ``sun_times``: a NumPy array, or a torch tensor on the object's GPU."""
-        if isinstance(buf, np.ndarray):
-            _typed(buf, np_dtype, 2, name)
-            return
-        if not hasattr(buf, "data_ptr"):
-            raise TypeError("Argument '%s' has incorrect type (expected numpy.ndarray or torch.Tensor, got %s)"
-                            % (name, type(buf).__name__))
-        if buf.dim() != 2:
-            raise ValueError("Buffer has wrong number of dimensions (expected 2, got %d)" % buf.dim())
-        if str(buf.dtype).split(".")[-1] != np.dtype(np_dtype).name:
-            raise ValueError("Buffer dtype mismatch, expected '%s' but got '%s'" % (np.dtype(np_dtype).name, buf.dtype))
-        if buf.device.type != "cuda" or buf.device.index != self.device:
-            raise ValueError("tensor '%s' is not on the HorizonTerrain's device (cuda:%d)" % (name, self.device))
+        _sw_dir_cor_coarse(self, "hz_horizon_terrain_sw_dir_cor_coarse", sun_positions, pixel_per_gc, f_cor, sunlit_frac)
 
     def sun_times(self, sun_positions, times, *, sunrise=None, sunset=None, duration=None, intervals=None):
         """Maps over a sun track (clause 14): sun_positions f32[S][3] (S >= 1) at the ``times``
@@ -657,17 +602,14 @@ class HorizonTerrain:
         method: a ray says whether the sun is hidden, not by how much it clears, so there is nothing to interpolate."""
         outs = (("sunrise", sunrise, np.float32), ("sunset", sunset, np.float32), ("duration", duration, np.float32),
                 ("intervals", intervals, np.int32))
-        self._accum_arg(sun_positions, 2, "sun_positions")
+        self._array_arg(sun_positions, 2, "sun_positions")
         _typed(times, np.float64, 1, "times")
         for name, buf, dtype in outs:
             if buf is not None:
-                self._sun_times_out(buf, dtype, name)
+                self._array_arg(buf, 2, name, dtype, self._NAME)
         if self._shape is None:
             raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
         given = [(name, buf) for name, buf, _ in outs if buf is not None]
-
-        def contiguous(a):
-            return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
         V.run((
             (ValueError, "at least one of 'sunrise', 'sunset', 'duration' and 'intervals' must be given", lambda: not given),
             (ValueError, "array 'sun_positions' has incorrect shape",
@@ -678,7 +620,7 @@ class HorizonTerrain:
             for name, buf in given
         ) + (
             (ValueError, "not all input arrays are C-contiguous",
-             lambda: not all(contiguous(a) for a in [sun_positions, times] + [buf for _, buf in given])),
+             lambda: not all(_contiguous(a) for a in [sun_positions, times] + [buf for _, buf in given])),
             (ValueError, "'sunrise', 'sunset', 'duration' and 'intervals' must be different arrays",
              lambda: len({ptr(buf) for _, buf in given}) != len(given)),
             (ValueError, "'times' must be finite and strictly increasing",

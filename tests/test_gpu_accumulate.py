@@ -179,6 +179,12 @@ def test_device_buffers_give_the_same_maps(hip):
     out = np.empty(mask.shape, np.float32)
     t.accumulate(d_sun, w, sunlit_sum=out)
     assert same(out, ref_lit)
+    # several chunks, each input from its own side: positions in HBM with host weights, and the other way round
+    for pos, wts in ((d_sun, w), (suns, d_w)):
+        with accum_chunk(2):
+            sw, lit = np.full(mask.shape, 7.0, np.float32), np.full(mask.shape, 7.0, np.float32)
+            t.accumulate(pos, wts, sw_dir_cor_sum=sw, sunlit_sum=lit)
+        assert same(sw, ref_sw) and same(lit, ref_lit)
 
 
 def test_terrain_on_a_shared_scene(hip):

@@ -196,6 +196,15 @@ def test_device_horizon_and_device_buffers_give_the_same_bytes(hip):
     torch.cuda.synchronize()
     assert same(o_sh.cpu().numpy(), sh) and same(o_sw.cpu().numpy(), sw)
     assert same(o_sum.cpu().numpy(), sum_sw) and same(o_lit.cpu().numpy(), sum_lit)
+    # several launches, each input from its own side: positions in HBM with host weights, and the other way round
+    d_sun, d_w = torch.from_numpy(suns).to(dev), torch.from_numpy(w).to(dev)
+    torch.cuda.synchronize()
+    for pos, wts in ((d_sun, w), (suns, d_w)):
+        a_sh, a_sw = np.full_like(sh, 9), np.full_like(sw, 9.0)
+        a_sum, a_lit = np.full(mask.shape, 9.0, np.float32), np.full(mask.shape, 9.0, np.float32)
+        with horisun_chunk(2):
+            td.accumulate(pos, wts, sw_dir_cor_sum=a_sum, sunlit_sum=a_lit, shadow_buffers=a_sh, sw_dir_cor_buffers=a_sw)
+        assert same(a_sh, sh) and same(a_sw, sw) and same(a_sum, sum_sw) and same(a_lit, sum_lit)
 
 
 def test_setup_is_terrains_bit_for_bit(hip):

@@ -640,6 +640,15 @@ def test_shadow_batch_matches_single(hip):
         b = np.empty(mask.shape, np.float32); t.sw_dir_cor(suns[s], b)
         assert np.array_equal(a, sb[s])
         assert np.array_equal(b, fb[s], equal_nan=True)
+    # the C entry point with the positions in HBM: the kernel reads them where they are
+    import ctypes
+    import torch
+    from horayzon_amd import _lib
+    d_suns = torch.from_numpy(suns).to("cuda:%d" % t.device)
+    torch.cuda.synchronize()
+    sd = np.full_like(sb, 77)
+    _lib.check(_lib.lib().hz_terrain_shadow_batch(t._h, d_suns.data_ptr(), 12, sd.ctypes.data, ctypes.byref(_lib.hz_stats())))
+    assert np.array_equal(sd, sb)
 
 
 def test_no_device_memory_leak(hip):

@@ -243,6 +243,15 @@ def test_torch_and_numpy_outputs_and_every_subset_give_the_same_words(hip):
         d_bad[5] = d_bad[4]
         assert L.hz_horizon_terrain_sun_times(t._h, suns.ctypes.data, d_bad.data_ptr(), suns.shape[0], C.byref(out), None) == 1
         assert b"strictly increasing" in L.hz_last_error()
+    # launches of two positions, each input from its own side: positions in HBM with host times, and the other way round
+    with chunk(2):
+        mixed = blank(t._shape)
+        t.sun_times(torch.from_numpy(suns).to("cuda:0"), times, **mixed)
+        assert same_words(mixed, want)
+        mixed = blank(t._shape)
+        out4 = _lib.hz_suntimes_out(**{k: v.ctypes.data for k, v in mixed.items()})
+        _lib.check(L.hz_horizon_terrain_sun_times(t._h, suns.ctypes.data, d_times.data_ptr(), suns.shape[0], C.byref(out4), None))
+        assert same_words(mixed, want)
 
 
 def test_c_entry_point_refuses_bad_arguments(hip):
