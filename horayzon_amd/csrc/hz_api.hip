@@ -199,65 +199,6 @@ int hz_scene_destroy(hz_scene *scene) {
     return HZ_OK;
 }
 
-static int topo_api(int kind, const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
-                    int len_2, float *out, int device) {
-    if (!azim || !hori || !out || (kind != 2 && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
-    // (the openness reads no azim[1] - azim[0]: one azimuth is enough, as in hz_topo_params and the reference)
-    if (len_0 <= 0 || len_1 <= 0 || len_2 < (kind == 2 ? 1 : 2)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
-    int rc = select_device(device);
-    if (rc) return rc;
-    hipStream_t st = nullptr;
-    const size_t ncell = (size_t)len_0 * len_1;
-    DevIn<float> d_azim, d_hori, d_tilt;
-    DevOut<float> d_out;
-    if ((rc = d_azim.bind(azim, (size_t)len_2, st))) return rc;
-    if ((rc = d_hori.bind(hori, ncell * (size_t)len_2, st))) return rc;
-    if (kind != 2) if ((rc = d_tilt.bind(vec_tilt, ncell * 3, st))) return rc;
-    if ((rc = d_out.bind(out, ncell))) return rc;
-    if ((rc = topo_launch(kind, d_azim.dev, d_hori.dev, d_tilt.dev, len_0, len_1, len_2, d_out.dev, st))) return rc;
-    if ((rc = d_out.finish(st))) return rc;
-    HZ_HIP(hipStreamSynchronize(st));
-    return HZ_OK;
-}
-
-int hz_sky_view_factor(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
-                       int len_2, float *svf, int device) {
-    return topo_api(0, azim, hori, vec_tilt, len_0, len_1, len_2, svf, device);
-}
-int hz_visible_sky_fraction(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
-                            int len_2, float *vsf, int device) {
-    return topo_api(1, azim, hori, vec_tilt, len_0, len_1, len_2, vsf, device);
-}
-int hz_topographic_openness(const float *azim, const float *hori, int len_0, int len_1, int len_2, float *top,
-                            int device) {
-    return topo_api(2, azim, hori, nullptr, len_0, len_1, len_2, top, device);
-}
-
-int hz_topo_params(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
-                   float *svf, float *vsf, float *openness, int device) {
-    const bool tilt = svf || vsf;
-    if (!svf && !vsf && !openness) return set_error(HZ_ERR_ARG, "no output requested (svf, vsf and openness are NULL)");
-    if (!azim || !hori || (tilt && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
-    if (len_0 <= 0 || len_1 <= 0 || len_2 < (tilt ? 2 : 1)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
-    int rc = select_device(device);
-    if (rc) return rc;
-    hipStream_t st = nullptr;
-    const size_t ncell = (size_t)len_0 * len_1;
-    DevIn<float> d_azim, d_hori, d_tilt;
-    DevOut<float> d_svf, d_vsf, d_open;
-    if ((rc = d_azim.bind(azim, (size_t)len_2, st))) return rc;
-    if ((rc = d_hori.bind(hori, ncell * (size_t)len_2, st))) return rc;
-    if (tilt) if ((rc = d_tilt.bind(vec_tilt, ncell * 3, st))) return rc;
-    if ((rc = d_svf.bind(svf, svf ? ncell : 0))) return rc;
-    if ((rc = d_vsf.bind(vsf, vsf ? ncell : 0))) return rc;
-    if ((rc = d_open.bind(openness, openness ? ncell : 0))) return rc;
-    if ((rc = topo_multi_launch(d_azim.dev, d_hori.dev, d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st)))
-        return rc;
-    if ((rc = d_svf.finish(st)) || (rc = d_vsf.finish(st)) || (rc = d_open.finish(st))) return rc;
-    HZ_HIP(hipStreamSynchronize(st));
-    return HZ_OK;
-}
-
 // ---------------------------------------------------------------------------------------
 // the azimuth-major layout (hz_planes.hip): planes[k][y][x] and hori[y][x][k] hold the same 32-bit word
 // ---------------------------------------------------------------------------------------
@@ -371,26 +312,15 @@ int hz_hori_quantise(const float *src, size_t n, uint16_t *dst, int device) { re
 
 int hz_hori_dequantise(const uint16_t *src, size_t n, float *dst, int device) { return q16_convert(false, src, n, dst, device); }
 
-// hz_topo_params on planes: rows [rb, re) of every plane back into a bounded cell-major buffer (k_planes_to_hori), then the
-// reduction launch hz_topo_params makes on it -- no numerics are written again, so every map is the same words
-int hz_topo_params_planes(const float *azim, const float *planes, const float *vec_tilt, int len_0, int len_1, int len_2,
-                          float *svf, float *vsf, float *openness, int device) {
-    const bool tilt = svf || vsf;
-    if (!svf && !vsf && !openness) return set_error(HZ_ERR_ARG, "no output requested (svf, vsf and openness are NULL)");
-    if (!azim || !planes || (tilt && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
-    if (len_0 <= 0 || len_1 <= 0 || len_2 < (tilt ? 2 : 1)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
-    int rc = planes_check_shape(azim, planes, len_0, len_1, len_2);
-    if (rc) return rc;
-    if ((rc = select_device(device))) return rc;
-    hipStream_t st = nullptr;
+// ---------------------------------------------------------------------------------------
+// the reductions over the azimuth axis (hz_topo.hip): three single-output entry points, hz_topo_params, hz_topo_params_planes
+// ---------------------------------------------------------------------------------------
+// The planes form: rows [rb, re) of every plane back into a bounded cell-major buffer (k_planes_to_hori), then the
+// reduction launch the cell-major form makes on it -- no numerics are written again, so every map is the same words.
+// azim, tilt and the outputs are device memory (tilt and the outputs may be null).
+static int topo_launch_planes(const float *azim, const float *planes, const float *tilt, int len_0, int len_1, int len_2,
+                              float *svf, float *vsf, float *openness, hipStream_t st) {
     const size_t ncell = (size_t)len_0 * len_1, A = (size_t)len_2;
-    DevIn<float> d_azim, d_tilt;
-    DevOut<float> d_svf, d_vsf, d_open;
-    if ((rc = d_azim.bind(azim, A, st))) return rc;
-    if (tilt) if ((rc = d_tilt.bind(vec_tilt, ncell * 3, st))) return rc;
-    if ((rc = d_svf.bind(svf, svf ? ncell : 0))) return rc;
-    if ((rc = d_vsf.bind(vsf, vsf ? ncell : 0))) return rc;
-    if ((rc = d_open.bind(openness, openness ? ncell : 0))) return rc;
     const bool planes_dev = is_device_ptr(planes);
     const int rows = (int)std::max<size_t>(1, planes_chunk_cells(ncell, len_2) / (size_t)len_1);
     const size_t chunk = (size_t)rows * len_1;
@@ -400,22 +330,74 @@ int hz_topo_params_planes(const float *azim, const float *planes, const float *v
     for (int rb = 0; rb < len_0; rb += rows) {
         const int re = std::min(rb + rows, len_0);
         const size_t c0 = (size_t)rb * len_1, n = (size_t)(re - rb) * len_1;
+        int rc;
         if (planes_dev) rc = planes_to_hori_launch(planes, ncell, c0, n, len_2, (float *)d_h.p, st);
         else {
             HZ_HIP(hipMemcpy2DAsync(d_p.p, n * sizeof(float), planes + c0, ncell * sizeof(float), n * sizeof(float), A,
                                     hipMemcpyHostToDevice, st));
             rc = planes_to_hori_launch((const float *)d_p.p, n, 0, n, len_2, (float *)d_h.p, st);
         }
-        if (!rc) rc = topo_multi_launch(d_azim.dev, (const float *)d_h.p, d_tilt.dev ? d_tilt.dev + 3 * c0 : nullptr, re - rb, len_1,
-                                        len_2, d_svf.dev ? d_svf.dev + c0 : nullptr, d_vsf.dev ? d_vsf.dev + c0 : nullptr,
-                                        d_open.dev ? d_open.dev + c0 : nullptr, st);
+        if (!rc) rc = topo_launch(azim, (const float *)d_h.p, tilt ? tilt + 3 * c0 : nullptr, re - rb, len_1, len_2,
+                                  svf ? svf + c0 : nullptr, vsf ? vsf + c0 : nullptr, openness ? openness + c0 : nullptr, st);
         if (rc) { (void)hipStreamSynchronize(st); return rc; }
         HZ_HIP(hipStreamSynchronize(st));           // the chunk buffers are used again
     }
+    return HZ_OK;
+}
+
+// The one driver of the five entry points.  `planes`: hori is planes[azim][y][x] (host or device), else cell-major.
+// `no_output`: the message when no output is asked for (a single-output entry point hands its one output in its slot).
+static int topo_api(bool planes, const char *no_output, const float *azim, const float *hori, const float *vec_tilt, int len_0,
+                    int len_1, int len_2, float *svf, float *vsf, float *openness, int device) {
+    const bool tilt = svf || vsf;
+    if (!svf && !vsf && !openness) return set_error(HZ_ERR_ARG, "%s", no_output);
+    if (!azim || !hori || (tilt && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
+    // (the openness reads no azim[1] - azim[0]: one azimuth is enough, as in the reference)
+    if (len_0 <= 0 || len_1 <= 0 || len_2 < (tilt ? 2 : 1)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
+    int rc;
+    if (planes && (rc = planes_check_shape(azim, hori, len_0, len_1, len_2))) return rc;
+    if ((rc = select_device(device))) return rc;
+    hipStream_t st = nullptr;
+    const size_t ncell = (size_t)len_0 * len_1;
+    DevIn<float> d_azim, d_hori, d_tilt;
+    DevOut<float> d_svf, d_vsf, d_open;
+    if ((rc = d_azim.bind(azim, (size_t)len_2, st))) return rc;
+    if (!planes) if ((rc = d_hori.bind(hori, ncell * (size_t)len_2, st))) return rc;
+    if (tilt) if ((rc = d_tilt.bind(vec_tilt, ncell * 3, st))) return rc;
+    if ((rc = d_svf.bind(svf, svf ? ncell : 0))) return rc;
+    if ((rc = d_vsf.bind(vsf, vsf ? ncell : 0))) return rc;
+    if ((rc = d_open.bind(openness, openness ? ncell : 0))) return rc;
+    rc = planes ? topo_launch_planes(d_azim.dev, hori, d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st)
+                : topo_launch(d_azim.dev, d_hori.dev, d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st);
+    if (rc) return rc;
     if ((rc = d_svf.finish(st)) || (rc = d_vsf.finish(st)) || (rc = d_open.finish(st))) return rc;
     HZ_HIP(hipStreamSynchronize(st));
     return HZ_OK;
 }
+
+static const char *const TOPO_NO_OUTPUT = "no output requested (svf, vsf and openness are NULL)";
+
+int hz_sky_view_factor(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
+                       int len_2, float *svf, int device) {
+    return topo_api(false, "NULL argument", azim, hori, vec_tilt, len_0, len_1, len_2, svf, nullptr, nullptr, device);
+}
+int hz_visible_sky_fraction(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
+                            int len_2, float *vsf, int device) {
+    return topo_api(false, "NULL argument", azim, hori, vec_tilt, len_0, len_1, len_2, nullptr, vsf, nullptr, device);
+}
+int hz_topographic_openness(const float *azim, const float *hori, int len_0, int len_1, int len_2, float *top,
+                            int device) {
+    return topo_api(false, "NULL argument", azim, hori, nullptr, len_0, len_1, len_2, nullptr, nullptr, top, device);
+}
+int hz_topo_params(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
+                   float *svf, float *vsf, float *openness, int device) {
+    return topo_api(false, TOPO_NO_OUTPUT, azim, hori, vec_tilt, len_0, len_1, len_2, svf, vsf, openness, device);
+}
+int hz_topo_params_planes(const float *azim, const float *planes, const float *vec_tilt, int len_0, int len_1, int len_2,
+                          float *svf, float *vsf, float *openness, int device) {
+    return topo_api(true, TOPO_NO_OUTPUT, azim, planes, vec_tilt, len_0, len_1, len_2, svf, vsf, openness, device);
+}
+
 
 // ---------------------------------------------------------------------------------------
 // test hooks for the build primitives (hz_sort.hip)

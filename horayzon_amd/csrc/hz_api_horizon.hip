@@ -848,15 +848,12 @@ int HorizonRun::chunk(int rb) {
     const int rc_b = e.trace_end.record(st);
     if (!rc) rc = rc_b;
     if (!rc && want_topo) {
-        // one reduction launch per chunk: k_topo<0> itself when the SVF is the only map, the fused kernel otherwise
+        // one reduction launch per chunk, whatever the maps (the SVF alone is k_topo<1>)
         const size_t o = (size_t)(rb - w.row_begin) * dim_in_1;
         const float *tilt_chunk = tilt0 ? tilt0 + 3 * (size_t)rb * dim_in_1 : nullptr;
-        if (!w.want_vsf && !w.want_open)
-            rc = svf_launch(d_azim.dev, hori_chunk, tilt_chunk, re - rb, dim_in_1, azim_num, d_svf.dev + o, st);
-        else
-            rc = topo_multi_launch(d_azim.dev, hori_chunk, tilt_chunk, re - rb, dim_in_1, azim_num,
-                                   w.want_svf ? d_svf.dev + o : nullptr, w.want_vsf ? d_vsf.dev + o : nullptr,
-                                   w.want_open ? d_open.dev + o : nullptr, st);
+        rc = topo_launch(d_azim.dev, hori_chunk, tilt_chunk, re - rb, dim_in_1, azim_num,
+                         w.want_svf ? d_svf.dev + o : nullptr, w.want_vsf ? d_vsf.dev + o : nullptr,
+                         w.want_open ? d_open.dev + o : nullptr, st);
     }
     const int rc_c = e.reduce_end.record(st);
     if (!rc) rc = rc_c;

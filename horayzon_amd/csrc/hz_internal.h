@@ -286,14 +286,11 @@ enum {
 int horizon_launch(const Scene *sc, const HorizonArgs &a, hipStream_t st, int *used_level_stack = nullptr);
 int left_sort(const HorizonArgs &a, int region, hipStream_t st);
 int horizon_num_blocks(const HorizonArgs &a);
-int topo_launch(int kind, const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
-                int len_2, float *out, hipStream_t st);
-int svf_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
-               int len_2, float *svf, hipStream_t st);
-// any subset of the three reductions from one pass over `hori`: the outputs that are not NULL are written (at least one;
-// vec_tilt is read when svf or vsf is); a single output launches k_topo<KIND> itself
-int topo_multi_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
-                      float *svf, float *vsf, float *openness, hipStream_t st);
+
+// hz_topo.hip: any subset of the three reductions over the azimuth axis from one pass over `hori`: the outputs that are
+// not NULL are written (at least one; vec_tilt is read when svf or vsf is)
+int topo_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
+                float *svf, float *vsf, float *openness, hipStream_t st);
 
 // hz_near.hip: near-field certificates (pre-pass of the horizon kernel)
 struct NearArgs {

@@ -25,12 +25,45 @@ def _contiguous_planes(hori):
     return hori
 
 
-def _one_from_planes(kind, azim, hori, vec_tilt, shape, device):
-    out = np.empty(shape, dtype=np.float32)
-    args = [None, None, None]
-    args[kind] = ptr(out)
-    _lib.check(_lib.lib().hz_topo_params_planes(ptr(azim), ptr(hori), ptr(vec_tilt), shape[0], shape[1], hori.shape[0],
-                                                *args, device))
+TOPO_NAMES = ("svf", "vsf", "openness")
+# a single output on a cell-major horizon keeps its own entry point (the exports stay exercised)
+_SINGLE = {"svf": "hz_sky_view_factor", "vsf": "hz_visible_sky_fraction", "openness": "hz_topographic_openness"}
+
+
+def _reduce(names, azim, hori, vec_tilt, device, layout, single=False):
+    """``{name: float32 (y, x)}`` for the ``names`` out of TOPO_NAMES: the reference's shape and dtype checks
+    (topo_param.pyx:398-404, :486-492, :565-569), the contiguity handling and the library call.  ``single``: ``names`` is
+    one name, and a cell-major horizon goes to that output's own entry point."""
+    tilted = "svf" in names or "vsf" in names
+    planes, cells, num = _cell_shape(hori, layout)
+    if tilted:
+        if (len(azim) != num) or (cells != vec_tilt.shape[:2])\
+                or (vec_tilt.shape[2] != 3):
+            raise ValueError("Inconsistent/incorrect shapes of input arrays")
+        if ((azim.dtype != "float32") or (hori.dtype != "float32")
+                or (vec_tilt.dtype != "float32")):
+            raise ValueError("Input array(s) has/have incorrect data type(s)")
+        if len(azim) < 2:   # azim[1] - azim[0] is read (topo_param.pyx:433, :520): out of bounds in the reference
+            raise ValueError("Inconsistent/incorrect shapes of input arrays")
+        vec_tilt = np.ascontiguousarray(vec_tilt)
+    else:
+        if len(azim) != num:
+            raise ValueError("Inconsistent/incorrect shapes of input arrays")
+        if (azim.dtype != "float32") or (hori.dtype != "float32"):
+            raise ValueError("Input array(s) has/have incorrect data type(s)")
+        vec_tilt = None
+    azim = np.ascontiguousarray(azim)
+    hori = _contiguous_planes(hori) if planes else np.ascontiguousarray(hori)
+    out = {n: np.empty(cells, dtype=np.float32) for n in TOPO_NAMES if n in names}
+    L = _lib.lib()
+    if single and not planes:
+        tilt_arg = (ptr(vec_tilt),) if tilted else ()
+        _lib.check(getattr(L, _SINGLE[names[0]])(ptr(azim), ptr(hori), *tilt_arg, cells[0], cells[1], num,
+                                                 ptr(out[names[0]]), device))
+    else:
+        _lib.check((L.hz_topo_params_planes if planes else L.hz_topo_params)(
+            ptr(azim), ptr(hori), ptr(vec_tilt), cells[0], cells[1], num, ptr(out.get("svf")), ptr(out.get("vsf")),
+            ptr(out.get("openness")), device))
     return out
 
 
@@ -42,70 +75,19 @@ def sky_view_factor(azim, hori, vec_tilt, *, device=0, layout="cell_major"):
     [radian], vec_tilt float32 (y, x, 3); returns svf float32 (y, x).  With
     ``layout="azim_major"`` (not in the reference) hori is float32 (azim, y, x), C-contiguous; the result is the
     same, bit for bit."""
-    planes, cells, num = _cell_shape(hori, layout)
-    # Check arguments (topo_param.pyx:398-404)
-    if (len(azim) != num) or (cells != vec_tilt.shape[:2])\
-            or (vec_tilt.shape[2] != 3):
-        raise ValueError("Inconsistent/incorrect shapes of input arrays")
-    if ((azim.dtype != "float32") or (hori.dtype != "float32")
-            or (vec_tilt.dtype != "float32")):
-        raise ValueError("Input array(s) has/have incorrect data type(s)")
-    if len(azim) < 2:   # azim[1] - azim[0] is read (topo_param.pyx:433): out of bounds in the reference
-        raise ValueError("Inconsistent/incorrect shapes of input arrays")
-    azim = np.ascontiguousarray(azim)
-    vec_tilt = np.ascontiguousarray(vec_tilt)
-    if planes:
-        return _one_from_planes(0, azim, _contiguous_planes(hori), vec_tilt, cells, device)
-    hori = np.ascontiguousarray(hori)
-    svf = np.empty(hori.shape[:2], dtype=np.float32)
-    _lib.check(_lib.lib().hz_sky_view_factor(ptr(azim), ptr(hori), ptr(vec_tilt),
-                                             hori.shape[0], hori.shape[1], hori.shape[2],
-                                             ptr(svf), device))
-    return svf
+    return _reduce(["svf"], azim, hori, vec_tilt, device, layout, single=True)["svf"]
 
 
 def visible_sky_fraction(azim, hori, vec_tilt, *, device=0, layout="cell_major"):
     """Visible sky fraction (solid angle of the visible sky); arguments, checks and result as the
     reference (topo_param.pyx:465-496); ``layout`` as in ``sky_view_factor``."""
-    planes, cells, num = _cell_shape(hori, layout)
-    if (len(azim) != num) or (cells != vec_tilt.shape[:2])\
-            or (vec_tilt.shape[2] != 3):
-        raise ValueError("Inconsistent/incorrect shapes of input arrays")
-    if ((azim.dtype != "float32") or (hori.dtype != "float32")
-            or (vec_tilt.dtype != "float32")):
-        raise ValueError("Input array(s) has/have incorrect data type(s)")
-    if len(azim) < 2:   # azim[1] - azim[0] is read (topo_param.pyx:520): out of bounds in the reference
-        raise ValueError("Inconsistent/incorrect shapes of input arrays")
-    azim = np.ascontiguousarray(azim)
-    vec_tilt = np.ascontiguousarray(vec_tilt)
-    if planes:
-        return _one_from_planes(1, azim, _contiguous_planes(hori), vec_tilt, cells, device)
-    hori = np.ascontiguousarray(hori)
-    vsf = np.empty(hori.shape[:2], dtype=np.float32)
-    _lib.check(_lib.lib().hz_visible_sky_fraction(ptr(azim), ptr(hori), ptr(vec_tilt), hori.shape[0],
-                                                  hori.shape[1], hori.shape[2], ptr(vsf), device))
-    return vsf
+    return _reduce(["vsf"], azim, hori, vec_tilt, device, layout, single=True)["vsf"]
 
 
 def topographic_openness(azim, hori, *, device=0, layout="cell_major"):
     """Positive topographic openness (Yokoyama et al. 2002) [radian]; arguments, checks and result as
     the reference (topo_param.pyx:548-574); ``layout`` as in ``sky_view_factor``."""
-    planes, cells, num = _cell_shape(hori, layout)
-    if len(azim) != num:
-        raise ValueError("Inconsistent/incorrect shapes of input arrays")
-    if (azim.dtype != "float32") or (hori.dtype != "float32"):
-        raise ValueError("Input array(s) has/have incorrect data type(s)")
-    azim = np.ascontiguousarray(azim)
-    if planes:
-        return _one_from_planes(2, azim, _contiguous_planes(hori), None, cells, device)
-    hori = np.ascontiguousarray(hori)
-    top = np.empty(hori.shape[:2], dtype=np.float32)
-    _lib.check(_lib.lib().hz_topographic_openness(ptr(azim), ptr(hori), hori.shape[0], hori.shape[1],
-                                                  hori.shape[2], ptr(top), device))
-    return top
-
-
-TOPO_NAMES = ("svf", "vsf", "openness")
+    return _reduce(["openness"], azim, hori, None, device, layout, single=True)["openness"]
 
 
 def topo_parameters(azim, hori, vec_tilt=None, which=TOPO_NAMES, *, device=0, layout="cell_major"):
@@ -121,35 +103,9 @@ def topo_parameters(azim, hori, vec_tilt=None, which=TOPO_NAMES, *, device=0, la
     unknown = [n for n in names if n not in TOPO_NAMES]
     if unknown:
         raise ValueError("unknown name(s) in 'which': %r (choose from %r)" % (unknown, TOPO_NAMES))
-    tilted = "svf" in names or "vsf" in names
-    if tilted and vec_tilt is None:
+    if ("svf" in names or "vsf" in names) and vec_tilt is None:
         raise ValueError("'svf' and 'vsf' need 'vec_tilt'")
-    planes, cells, num = _cell_shape(hori, layout)
-    # Check arguments (topo_param.pyx:398-404 / :565-569)
-    if tilted:
-        if (len(azim) != num) or (cells != vec_tilt.shape[:2])\
-                or (vec_tilt.shape[2] != 3):
-            raise ValueError("Inconsistent/incorrect shapes of input arrays")
-        if ((azim.dtype != "float32") or (hori.dtype != "float32")
-                or (vec_tilt.dtype != "float32")):
-            raise ValueError("Input array(s) has/have incorrect data type(s)")
-        if len(azim) < 2:   # azim[1] - azim[0] is read (topo_param.pyx:433, :520)
-            raise ValueError("Inconsistent/incorrect shapes of input arrays")
-        vec_tilt = np.ascontiguousarray(vec_tilt)
-    else:
-        if len(azim) != num:
-            raise ValueError("Inconsistent/incorrect shapes of input arrays")
-        if (azim.dtype != "float32") or (hori.dtype != "float32"):
-            raise ValueError("Input array(s) has/have incorrect data type(s)")
-        vec_tilt = None
-    azim = np.ascontiguousarray(azim)
-    hori = _contiguous_planes(hori) if planes else np.ascontiguousarray(hori)
-    out = {n: np.empty(cells, dtype=np.float32) for n in TOPO_NAMES if n in names}
-    L = _lib.lib()
-    _lib.check((L.hz_topo_params_planes if planes else L.hz_topo_params)(
-        ptr(azim), ptr(hori), ptr(vec_tilt), cells[0], cells[1], num, ptr(out.get("svf")), ptr(out.get("vsf")),
-        ptr(out.get("openness")), device))
-    return out
+    return _reduce(names, azim, hori, vec_tilt, device, layout)
 
 
 def _slope(which, x, y, z, rot_mat, output_rot, device):

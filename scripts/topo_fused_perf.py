@@ -4,8 +4,8 @@
     python scripts/topo_fused_perf.py --c5 [--tile 14401] [--out FILE]
 
 One warm-up and one timed step of each of
-  - dev_svf:        the bench.py step: device-resident horizon + the SVF (k_topo<0>)
-  - dev_all:        the same + VSF and openness through hz_topo_out (the fused kernel, one launch)
+  - dev_svf:        the bench.py step: device-resident horizon + the SVF (k_topo<1>, hz_topo.hip)
+  - dev_all:        the same + VSF and openness through hz_topo_out (k_topo<7>, one launch)
   - svf_only:       horizon never materialised (skip_hori), SVF only -- today's path for mosaics that do not fit
   - topo_only_all:  horizon never materialised, all three maps from one fused launch per chunk
   - separate_x3:    three hz_topo_params calls, one output each, on the materialised device horizon of dev_svf

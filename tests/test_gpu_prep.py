@@ -29,9 +29,9 @@ def test_visible_sky_fraction_and_openness(hip):
 
 
 def test_topo_kernels_agree_with_each_other(hip):
-    """The tiled kernel (k_topo: azimuth tables in LDS, float32 arctangent only where the tilted plane limits) and the
-    fallback for very large azimuth counts (k_topo_wide: libm's float64 routines per azimuth, as the Cython code) must not
-    drift apart: same fixtures, both within 1e-5 of the reference's values and within 2e-6 of each other."""
+    """The tiled kernel (k_topo of hz_topo.hip: azimuth tables in LDS, float32 arctangent only where the tilted plane
+    limits) and the fallback for very large azimuth counts (k_topo_wide: libm's float64 routines per azimuth, as the
+    Cython code) must not drift apart: same fixtures, both within 1e-5 of the reference's values and within 2e-6 of each other."""
     d = np.load(os.path.join(os.path.dirname(GOLD), "svf_reference.npz"))
     T = hip.topo_param
     for n in "abc":

@@ -1,5 +1,5 @@
-"""Every instantiation of the horizon reductions -- k_topo<0|1|2>, k_topo_wide<0|1|2>, k_topo_multi<WANT>,
-k_topo_multi_wide<WANT> (horayzon_amd/csrc/hz_horizon.hip) -- against the float64 NumPy reference of
+"""Every instantiation of the horizon reductions -- k_topo<WANT> and k_topo_wide<WANT>, a single output being WANT = 1, 2
+or 4 (horayzon_amd/csrc/hz_topo.hip) -- against the float64 NumPy reference of
 tests/topo_reference.py (pinned to the real program's outputs by tests/test_topo_reference.py), not against each other.
 
 Every case runs through the three single-output entry points, topo_parameters for all three maps and for each pair, each in
