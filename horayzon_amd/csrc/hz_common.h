@@ -587,6 +587,15 @@ __device__ __forceinline__ void hz_entry_unpack(int e, int &pf, int &pm) {
 //   the way in), the caller stores the sentinel once per block (nothing ever overwrites entry 0), `regroup` is hz_n_leave_pack's
 //   word (regroup_rule is not read), the node's address is formed from the zero-extended link (a node link is never negative: no
 //   sign-extending shift), and the x and y pair-1 selectors are formed once per call (hz_node_hit_masks_t<true>).
+// Two build switches of the LEAN form, both on and both meant to stay: 0 compiles the plain form's text for that part, which is how
+// each was measured alone (scripts/build_variant.sh; DESIGN.md section 0: the loop top 1.4 %, the join 1.7 %) and how it can be measured
+// again after a compiler upgrade.  The instruction counts in the comments below were read from hipcc of ROCm 7.2 (AMD clang 22.0.0git).
+#ifndef HZ_LEAN_NODE_JOIN
+#define HZ_LEAN_NODE_JOIN 1     // 0: LEAN keeps the node step's branch nested in the vote's, the leaf step as its else
+#endif
+#ifndef HZ_LEAN_LOOP_TOP
+#define HZ_LEAN_LOOP_TOP 1      // 0: LEAN keeps the plain form's queue fills
+#endif
 template <int TPB, bool COUNT, int QLEN = 2, bool NODELET = false, bool LEVELSTACK = true, bool LEND = false, bool LEAN = false>
 __device__ __forceinline__ int hz_trace(const Node *__restrict__ nodes, const Prim *__restrict__ prims,
                                         const float4 *top, int ntop, int *stack, int tid,
@@ -647,6 +656,8 @@ typedef __attribute__((address_space(3))) int hz_lds_int;
     unsigned long long m_node, m_leaf;
     int n_all;
     auto top_of_iteration = [&]() __attribute__((always_inline)) {
+        bool can_leaf_top = false;                  // (LEAN: the leaf vote, taken early below)
+        unsigned long long m_leaf_top = 0ull;
         // set leaves aside while the leaf queue (QLEN entries, filled front to back; a queued leaf is negative, an empty
         // place HZ_EMPTY) has room
         if (LEVELSTACK) {
@@ -668,136 +679,74 @@ typedef __attribute__((address_space(3))) int hz_lds_int;
 #define HZ_SELM(m, x, y) (((m) & (x)) | (~(m) & (y)))
             int m1 = (node & ~lq0) >> 31;
             asm volatile("" : "+v"(m1));          // (the compiler must not know that this is 0 / -1)
-            lq0 = HZ_SELM(m1, node, lq0); node = HZ_SELM(m1, t0, node); t0 = HZ_SELM(m1, t1, t0); sa -= (unsigned)m1 & (unsigned)(TPB * 4);
+            // LEAN: four instructions fewer than the plain form, which stays for every other instantiation --
+            //  * the second mask from the SELECTED node (pinned: left alone the compiler expands the select into the mask's operand,
+            //    (m1 & t0 | node & ~m1) & ~lq1, three instructions in front of the shift, although the select itself follows one
+            //    instruction later);
+            //  * one stack-pointer update from the sum of the two masks (0, -1 or -2 rows): an add and a shift-add instead of two
+            //    ANDs, an add and a subtract.
+            // The compiler takes a register that an asm block defines for one with a forwarding hazard and pads with an s_nop when
+            // the next instruction reads it; it does not move an independent instruction there by itself.  The two there are -- the
+            // leaf vote's compare and the select of the entry below the top -- are held behind the two pins with scheduling barriers
+            // (they emit nothing).
+            constexpr bool lean_top = LEAN && HZ_LEAN_LOOP_TOP;
+            static_assert(!lean_top || (TPB * 4 & (TPB * 4 - 1)) == 0, "a stack row must be a power of two of bytes: the masks' sum is shifted");
+            lq0 = HZ_SELM(m1, node, lq0); node = HZ_SELM(m1, t0, node);
+            if (lean_top) {
+                asm volatile("" : "+v"(node));
+                __builtin_amdgcn_sched_barrier(0);
+                can_leaf_top = lq0 < 0; m_leaf_top = __ballot(can_leaf_top);
+                __builtin_amdgcn_sched_barrier(0);
+            } else { t0 = HZ_SELM(m1, t1, t0); sa -= (unsigned)m1 & (unsigned)(TPB * 4); }
             int m2 = (node & ~lq1) >> 31;
             asm volatile("" : "+v"(m2));
-            lq1 = HZ_SELM(m2, node, lq1); node = HZ_SELM(m2, t0, node); sa -= (unsigned)m2 & (unsigned)(TPB * 4);
+            if (lean_top) {
+                __builtin_amdgcn_sched_barrier(0);
+                t0 = HZ_SELM(m1, t1, t0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            lq1 = HZ_SELM(m2, node, lq1); node = HZ_SELM(m2, t0, node);
+            if (lean_top) sa += (unsigned)(m1 + m2) << __builtin_ctz((unsigned)(TPB * 4));
+            else sa -= (unsigned)m2 & (unsigned)(TPB * 4);
 #undef HZ_SELM
         }
         can_node = HZ_IS_NODE(node);
-        can_leaf = lq0 < 0;
+        can_leaf = (LEAN && HZ_LEAN_LOOP_TOP) ? can_leaf_top : lq0 < 0;
         // votes taken before any lane leaves: a lane that is finished contributes to neither mask, so the
         // masks equal those of the lanes that stay (and stay plain scalar compares)
-        m_node = __ballot(can_node); m_leaf = __ballot(can_leaf);
+        m_node = __ballot(can_node); m_leaf = (LEAN && HZ_LEAN_LOOP_TOP) ? m_leaf_top : __ballot(can_leaf);
         n_all = __popcll(m_node | m_leaf);
     };
     top_of_iteration();
     while (n_all >= n_leave) {
         const int n_node = __popcll(m_node);
         const int n_leaf = __popcll(m_leaf);
+        // (the two steps are text of their own, hz_trace_node_step.inc and hz_trace_leaf_step.inc, so that the loop can hold them in
+        //  either control form)
+        if (LEAN && HZ_LEAN_NODE_JOIN) {
+            // One exec-mask branch around the node step, taken by the lanes with a node when the wave votes for it, instead of that
+            // branch inside a scalar one with the leaf step as its else: the join of the nested form has a side on which the
+            // step's results are undefined, and the register allocator then gives them registers of their own -- three copies in
+            // front of the node step, two behind it, one behind the leaf step.  Here the step writes `node`, `sa` and `sa_hi` in
+            // place.  The same lanes run the step as before.  The leaf step's scalar branch compares the vote again (through a copy
+            // the compiler cannot see through, or it keeps the first compare as a lane mask: two more scalar instructions).
+            int vote_node = n_node * 16;
+            const int vote_leaf = n_leaf * leaf_bias;
+            if (vote_node >= vote_leaf && can_node) {
+#include "hz_trace_node_step.inc"
+            }
+            asm volatile("" : "+s"(vote_node));
+            if (vote_node < vote_leaf) {
+#include "hz_trace_leaf_step.inc"
+            }
+        } else
         if (n_node * 16 >= n_leaf * leaf_bias) {
             // ---------------- node step ------------------------------------------------------
             if (can_node) {
-                float4 n0; uint4 n1;
-                // NODELET: top-of-tree nodes from LDS, the rest from global memory (two separate asm paths:
-                // a per-lane pointer select would be compiled into slow flat loads).  Measured 2 % slower
-                // than plain global loads -- the top of the tree is L1 resident -- so it is opt-in.
-                if (NODELET && node < ntop) hz_load_node_lds(top + 2 * node, n0, n1);
-                else if (LEAN) hz_load_node(nodes + (unsigned)node, n0, n1);      // (no sign extension; v_lshl_add_u64 shifts by 4 at most: two instructions)
-                else hz_load_node(nodes + node, n0, n1);
-                if (COUNT) { cnt.nodes++; HZ_WAVE_TICK(cnt.w_nodes, lane); }
-                const NodeRay nr = hz_node_ray(rb, n0.x, n0.y, n0.z);
-                // children are visited in slot order (quadrant order).  A front-to-back order (slot r ^ direction
-                // signs, ~45 VALU per step) was measured to be a net loss: these are any-hit rays, a blocked ray
-                // is blocked over a long stretch behind the first ridge, and near-horizon rays that only
-                // nick a crest are served by the hit cache.  (Rounds 2-3 stored the tallest child first: +1 %; the
-                // quadrant order is what lets x and y share one range per half, i.e. the 32 B node.)
-                const int first = __float_as_int(n0.w);
-                if (LEVELSTACK) {
-                    bool h0, h1, h2, h3;
-                    hz_node_hits(nr, rb, tfar_box, n1, h0, h1, h2, h3);
-                    const int h = (h0 ? 1 : 0) | (h1 ? 2 : 0) | (h2 ? 4 : 0) | (h3 ? 8 : 0);
-                    if (h != 0) {                    // the hit children become the pending set of this level ...
-                        if (pm != 0) { stack[sp * TPB + tid] = hz_entry_pack(pf, pm); sp++; }
-                        pf = first; pm = h;
-                    }
-                    HZ_POP();                        // ... and the first of them (or of a level above) is entered
-                } else {
-                    int m0, m1, m2, m3;              // lane masks: all ones = child hit (hz_node_hit_masks)
-                    if (LEAN) hz_node_hit_masks_t<true>(nr, rb, sel_x1, sel_y1, tfar_box, n1, m0, m1, m2, m3);
-                    else hz_node_hit_masks(nr, rb, tfar_box, n1, m0, m1, m2, m3);
-                    // out of entries: remember the highest pointer (checked once, at the exit) and clamp
-                    sa_hi = max(sa_hi, sa);
-                    sa = min(sa, sa_cap);
-                    // Pushes without a branch, without scalar logic and (round 5) without compares: the three candidates are
-                    // always stored above the top and only kept (pointer advanced) when they were real links, i.e. when a
-                    // higher slot was hit too.  The hit masks become 0 / one-entry steps (a_k = m_k & S), "a higher slot was
-                    // hit" is an OR of those, "advance" an AND; the link that continues is picked with bit selects (m ? x : y
-                    // = v_bfi_b32); the lane without a hit child continues with the top entry pv and steps down.
-                    const unsigned S = (unsigned)(TPB * 4);
-                    const int pv = HZ_STACK_AT(sa + S);
-                    const unsigned a0 = (unsigned)m0 & S, a1 = (unsigned)m1 & S, a2 = (unsigned)m2 & S, a3 = (unsigned)m3 & S;
-                    const unsigned o32 = a3 | a2, o321 = o32 | a1, o3210 = o321 | a0;
-#define HZ_SEL(m, x, y) (((m) & (x)) | (~(m) & (y)))
-                    int next = HZ_SEL(m3, first + 3, pv);
-                    HZ_STACK_AT(sa + 2u * S) = next; sa += a2 & a3;   next = HZ_SEL(m2, first + 2, next);
-                    HZ_STACK_AT(sa + 2u * S) = next; sa += a1 & o32;  next = HZ_SEL(m1, first + 1, next);
-                    HZ_STACK_AT(sa + 2u * S) = next; sa += a0 & o321; next = HZ_SEL(m0, first, next);
-#undef HZ_SEL
-                    node = next; sa = sa + o3210 - S;
-                }
+#include "hz_trace_node_step.inc"
             }
         } else {
-            // ---------------- leaf step: the two triangles of a DEM quad (or one TIN triangle) ---
-            if (LEND && !LEVELSTACK) {
-                // 72 % of the lanes that test a leaf hold a second one (lq1) that would wait for another leaf step, while the
-                // lanes without a leaf idle through this one.  Every lane of the loop tells its partner (lane ^ 1, one DPP move:
-                // no LDS, no memory wait) what it holds: its second link (negative), "nothing queued" (HZ_EMPTY) or -- a lane
-                // without a leaf -- 1 = "idle".  A partner outside the loop reads as 0: neither a link nor "idle".
-                static_assert(HZ_EMPTY > 1, "the idle word must be neither a queued link (negative) nor HZ_EMPTY");
-                // One block of straight VALU code for the exchange and the helper's operands: vcc = the lanes with a leaf;
-                // w = can_leaf ? lq1 : 1; the ray a lane tests with = can_leaf ? its own : the partner's (v_cndmask_b32_dpp: the move
-                // and its select in one instruction; a lane that is neither owner nor helper forms values nobody uses);
-                // p_w = the partner's w (0 = the old value where the partner is outside the loop); lf = can_leaf ? lq0 : p_w.
-                // Hazards, by hand (the compiler's hazard recogniser does not look inside an asm block): a DPP read of a VGPR needs
-                // two wait states after the VALU write of it.  w (in lf) is written six instructions before v_mov_b32_dpp reads
-                // it; ox ... dz are written at the refill only, outside this loop, and two instructions of the block come first.
-                int p_w = 0, lf;
-                float rox, roy, roz, rdx, rdy, rdz;
-#define HZ_DPP_SEL(d, x) "v_cndmask_b32_dpp %[" d "], %[" x "], %[" x "], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                asm volatile("s_mov_b64 vcc, %[m]\n\t"
-                             "v_cndmask_b32_e32 %[lf], 1, %[lq1], vcc\n\t"
-                             HZ_DPP_SEL("rox", "ox") HZ_DPP_SEL("roy", "oy") HZ_DPP_SEL("roz", "oz")
-                             HZ_DPP_SEL("rdx", "dx") HZ_DPP_SEL("rdy", "dy") HZ_DPP_SEL("rdz", "dz")
-                             "v_mov_b32_dpp %[pw], %[lf] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                             "v_cndmask_b32_e32 %[lf], %[pw], %[lq0], vcc"
-                             : [pw] "+&v"(p_w), [lf] "=&v"(lf), [rox] "=&v"(rox), [roy] "=&v"(roy), [roz] "=&v"(roz),
-                               [rdx] "=&v"(rdx), [rdy] "=&v"(rdy), [rdz] "=&v"(rdz)
-                             : [m] "s"(m_leaf), [lq0] "v"(lq0), [lq1] "v"(lq1), [ox] "v"(ox), [oy] "v"(oy), [oz] "v"(oz),
-                               [dx] "v"(dx), [dy] "v"(dy), [dz] "v"(dz)
-                             : "vcc");
-#undef HZ_DPP_SEL
-                const bool helper = !can_leaf && p_w < 0;                   // tests the partner's second leaf with the partner's ray
-                const bool helped = can_leaf && lq1 < 0 && p_w == 1;        // this lane's second leaf is tested by the partner now
-                if (COUNT && lcnt && can_leaf && lq1 < 0 && p_w != 1) lcnt->unhelped++;
-                if (can_leaf || helper) {
-                    float4 q0, q1, q2;
-                    hz_load_prim(prims + HZ_LEAF_ID(lf), q0, q1, q2);
-                    if (COUNT) { cnt.tris += (q2.y == q2.y) ? 2 : 1; HZ_WAVE_TICK(cnt.w_leaves, lane); if (lcnt && helper) lcnt->lent++; }
-                    const bool hit = hz_quad_hit(rox, roy, roz, rdx, rdy, rdz, tfar, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w,
-                                                 q2.x, q2.y, q2.z, q2.w, q2.y == q2.y);
-                    // the helper's decision goes back the same way (only read by a lane whose partner is its helper, i.e. is here)
-                    const int p_hit = __builtin_amdgcn_update_dpp(0, hit ? 1 : 0, 0xB1, 0xF, 0xF, true);
-                    // owner: blocked by its own leaf, or by the lent one; else the queue moves up (the lent leaf is done with).
-                    // A helper's own state does not change.
-                    const bool lent_hit = helped && p_hit != 0;
-                    const bool any = hit || lent_hit;
-                    const int n_lq0 = any ? HZ_LEAF_ID(hit ? lq0 : lq1) : (helped ? HZ_EMPTY : lq1);
-                    node = (can_leaf && any) ? HZ_EMPTY : node;
-                    lq1 = (can_leaf && !any) ? HZ_EMPTY : lq1;
-                    lq0 = can_leaf ? n_lq0 : lq0;
-                }
-            } else
-            if (can_leaf) {
-                float4 q0, q1, q2;
-                hz_load_prim(prims + HZ_LEAF_ID(lq0), q0, q1, q2);
-                // a = (q0.x q0.y q0.z) b = (q0.w q1.x q1.y) c = (q1.z q1.w q2.x) d = (q2.y q2.z q2.w)
-                if (COUNT) { cnt.tris += (q2.y == q2.y) ? 2 : 1; HZ_WAVE_TICK(cnt.w_leaves, lane); }
-                const bool hit = hz_quad_hit(ox, oy, oz, dx, dy, dz, tfar, q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w,
-                                             q2.x, q2.y, q2.z, q2.w, q2.y == q2.y);
-                if (hit) { lq0 = HZ_LEAF_ID(lq0); node = HZ_EMPTY; }     // decided: blocked by this leaf
-                else { lq0 = lq1; lq1 = HZ_EMPTY; }
-            }
+#include "hz_trace_leaf_step.inc"
         }
         top_of_iteration();
     }
