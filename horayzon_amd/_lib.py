@@ -89,6 +89,7 @@ SYMBOLS = (
     "hz_slope_plane_meth", "hz_slope_vector_meth", "hz_lonlat2ecef", "hz_ecef2enu", "hz_wgs2swiss", "hz_swiss2wgs",
     "hz_ecef2enu_vector", "hz_surf_norm", "hz_north_dir", "hz_vert_grid_len", "hz_pack_vertices",
     "hz_debug_sort_pairs", "hz_debug_exclusive_scan",
+    "hz_debug_crmath_eval", "hz_debug_crmath_range", "hz_debug_refrac_factor",
     "hz_debug_valu_peak", "hz_debug_copy_peak", "hz_debug_inst_rate", "hz_debug_set",
     "hz_terrain_create", "hz_terrain_initialise", "hz_terrain_initialise_scene",
     "hz_terrain_shadow", "hz_terrain_sw_dir_cor", "hz_terrain_shadow_batch",
@@ -208,6 +209,9 @@ def lib():
     L.hz_pack_vertices.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, ip]
     L.hz_debug_sort_pairs.argtypes = [vp, vp, C.c_size_t, ip]
     L.hz_debug_exclusive_scan.argtypes = [vp, vp, C.c_size_t, ip]
+    L.hz_debug_crmath_eval.argtypes = [ip, vp, vp, vp, C.c_size_t, ip]
+    L.hz_debug_crmath_range.argtypes = [ip, C.c_uint32, C.c_uint32, C.c_size_t, C.c_float, vp, ip]
+    L.hz_debug_refrac_factor.argtypes = [vp, C.c_size_t, vp, ip]
     L.hz_debug_valu_peak.argtypes = [ip, ip, ip, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.hz_debug_copy_peak.argtypes = [ip, C.c_size_t, C.POINTER(C.c_double)]
     L.hz_debug_inst_rate.argtypes = [ip, ip, C.POINTER(C.c_double)]

@@ -7,7 +7,11 @@
  * platforms ship other routines -- there is no single "reference value" to be bit-equal to.  The contract
  * here is the CORRECTLY ROUNDED float result.  Each function evaluates in float64 with plain + - * / sqrt in
  * a fixed order (both users compile with -ffp-contract=off) to a relative error < 1e-14 and rounds once, so
- *   - the HIP kernels and the CPU oracle, which both include this header, agree bit for bit by construction;
+ *   - the HIP kernels and the CPU oracle, which both include this header, agree bit for bit -- as long as both compilers
+ *     keep to IEEE: the device's float64 sqrt and `/` are instruction sequences hipcc expands (v_rsq_f64 / v_rcp_f64, Newton
+ *     steps, v_div_fixup), a different program from gcc's sqrtsd / divsd.  tests/test_gpu_crmath.py pins them: the device
+ *     build alone (hz_crmath_probe.hip) against the oracle's build, exhaustively over the ranges of this path, and against
+ *     the mpmath fixture tests/golden/crmath_reference.npz;
  *   - the result is the correctly rounded float except when the exact value lies within 1e-14 (relative) of a
  *     rounding boundary (about 1 argument in 1e7).
  * Only the argument ranges of this path are covered accurately: acos [-1, 1]; tan [0, 1.6] rad; sin / cos

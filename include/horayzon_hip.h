@@ -446,6 +446,17 @@ int hz_topo_params(const float *azim, const float *hori, const float *vec_tilt, 
 /* exclusive prefix sum); host arrays, in place / in -> out.  Not needed by a binding.            */
 int hz_debug_sort_pairs(uint32_t *keys, uint32_t *vals, size_t n, int device);
 int hz_debug_exclusive_scan(const uint32_t *in, uint32_t *out, size_t n, int device);
+/* Test hooks for the device build of the refraction math (hz_crmath.h, hz_horisun_refrac.h; hz_crmath_probe.hip): one thread */
+/* per element, host arrays in and out; n == 0 succeeds without a launch and writes nothing.  Not needed by a binding.        */
+/* `which`: 0 hz_crm_acosf, 1 hz_crm_tanf, 2 hz_crm_cosf, 3 hz_crm_sinf, 4 hz_crm_powf(x, y), 5 horisun_deg2rad_f,             */
+/* 6 horisun_rad2deg_f, 7 horisun_atmos_refrac(x, (double)y).                                                                  */
+/* hz_debug_crmath_eval: out[i] = f(x[i], y[i]); y may be NULL (then 0) for the one-argument functions.                        */
+/* hz_debug_crmath_range: out[i] = f(the float with the bit pattern first_bits + i * stride (uint32 arithmetic), y) -- a sweep */
+/* uploads nothing.  hz_debug_refrac_factor: the per-cell float64 pressure / temperature factor of the refraction formula     */
+/* from elevation[n] [m], by the kernel Terrain and HorizonTerrain.refraction run.                                            */
+int hz_debug_crmath_eval(int which, const float *x, const float *y, float *out, size_t n, int device);
+int hz_debug_crmath_range(int which, uint32_t first_bits, uint32_t stride, size_t n, float y, float *out, int device);
+int hz_debug_refrac_factor(const float *elevation, size_t n, double *out_f64, int device);
 /* Machine calibration for the roofline (bench.py, untimed section).  hz_debug_valu_peak: chains of      */
 /* independent v_fma_f32 (packed = 1: v_pk_fma_f32) at 8 waves per SIMD, `waves_per_simd` rounds of      */
 /* 3.5 ms (the name is historical: it only sets the length of the run; long pure-FMA runs are power-     */

@@ -65,7 +65,7 @@ int orc_get_quad_order(void) { return g_quad_order; }
 #define ORC_BOX_START_PADS 16.0f
 static float g_box_start_pads = ORC_BOX_START_PADS;
 void orc_set_box_start(float tau_pads) { g_box_start_pads = tau_pads; }
-/* mode 0: hz_crmath.h (shared with the HIP kernels: GPU = oracle by construction); 1: the platform's float routines (what the
+/* mode 0: hz_crmath.h (shared with the HIP kernels; that the two compiles give the same words: tests/test_gpu_crmath.py); 1: the platform's float routines (what the
  * reference calls); 2: THE ORACLE'S OWN evaluation of the same contract -- the correctly rounded float -- through the x87
  * long double libm (64-bit mantissa, < 1 ulp of that: the rounding to float is correct unless the exact value lies within
  * ~1e-19 relative of a rounding boundary).  Mode 2 shares no code with the kernels: tests/test_gpu_parity.py::
@@ -1116,6 +1116,44 @@ static inline float atmos_refrac(float elev_ang_true, float temp, float pressure
     refrac_cor = (float)((double)refrac_cor + 0.0019279);
     refrac_cor = (float)((double)refrac_cor * (((double)pressure / 101.0) * (283.0 / (273.0 + (double)temp))));
     return (float)((double)refrac_cor * (1.0 / 60.0));
+}
+
+/* Host twin of the device probe (hz_crmath_probe.hip: hz_debug_crmath_eval / _range), element by element.  which: 0 acos, 1 tan,
+ * 2 cos, 3 sin, 4 pow(x, y) -- this file's compile of hz_crmath.h (orc_set_libm switches them as everywhere in this file);
+ * 5 deg2rad, 6 rad2deg, 7 atmos_refrac(x, (double)y) -- the reference's expressions with the IEEE `/`, NOT hz_crm_div_const,
+ * and the factor passed as a double as the kernels pass it.  tests/test_gpu_crmath.py requires the device's words to be these. */
+static inline float crmath_twin(int which, float x, float y) {
+    switch (which) {
+        case 0: return r_acosf(x);
+        case 1: return r_tanf(x);
+        case 2: return r_cosf(x);
+        case 3: return r_sinf(x);
+        case 4: return r_powf(x, y);
+        case 5: return deg2rad_f(x);
+        case 6: return rad2deg_f(x);
+        default: {
+            const float e = fmaxf(-1.0f, fminf(x, 90.0f));
+            float refrac_cor = (float)(1.02 / (double)r_tanf(deg2rad_f((float)((double)e + 10.3 / ((double)e + 5.11)))));
+            refrac_cor = (float)((double)refrac_cor + 0.0019279);
+            refrac_cor = (float)((double)refrac_cor * (double)y);
+            return (float)((double)refrac_cor * (1.0 / 60.0));
+        }
+    }
+}
+/* y may be NULL (then 0) */
+void orc_crmath_eval(int which, const float *x, const float *y, float *out, int64_t n) {
+#pragma omp parallel for
+    for (int64_t i = 0; i < n; i++) out[i] = crmath_twin(which, x[i], y ? y[i] : 0.0f);
+}
+/* element i: the float with the bit pattern first_bits + i * stride (uint32 arithmetic) */
+void orc_crmath_range(int which, uint32_t first_bits, uint32_t stride, int64_t n, float y, float *out) {
+#pragma omp parallel for
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t u = first_bits + (uint32_t)i * stride;
+        float x;
+        memcpy(&x, &u, 4);
+        out[i] = crmath_twin(which, x, y);
+    }
 }
 
 typedef struct {

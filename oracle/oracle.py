@@ -156,6 +156,34 @@ def crmath_sweep(which, lo, hi, y=0.0):
     return int(out[0]), int(out[1]), int(out[2])
 
 
+CRMATH_FUNCS = ("acos", "tan", "cos", "sin", "pow", "deg2rad", "rad2deg", "atmos_refrac")   # `which` of the device probe too
+
+
+def crmath_eval(which, x, y=None):
+    """Host twin of hz_debug_crmath_eval: f32 words of function `which` (index into CRMATH_FUNCS) at x (and y: pow's exponent /
+    atmos_refrac's factor).  0-4 follow set_libm; 5-7 are the reference's expressions with the IEEE division."""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.empty(x.shape, np.float32)
+    if y is not None:
+        y = np.ascontiguousarray(y, np.float32)
+        assert y.shape == x.shape
+    f = lib().orc_crmath_eval
+    f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    f.restype = None
+    f(int(which), x.ctypes.data, None if y is None else y.ctypes.data, out.ctypes.data, x.size)
+    return out
+
+
+def crmath_range(which, first_bits, stride, n, y=0.0):
+    """Host twin of hz_debug_crmath_range: element i is the float with the bit pattern first_bits + i * stride (mod 2^32)."""
+    out = np.empty(int(n), np.float32)
+    f = lib().orc_crmath_range
+    f.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_int64, C.c_float, C.c_void_p]
+    f.restype = None
+    f(int(which), int(first_bits), int(stride), int(n), float(y), out.ctypes.data)
+    return out
+
+
 def div_const_sweep(c, lo_bits, hi_bits):
     """hz_crmath.h's four-instruction division by the constant c > 0 against the IEEE division, for every float whose bit pattern
     lies in [lo_bits, hi_bits] (promoted to double).  Returns (values, differing results)."""
