@@ -101,7 +101,7 @@ SYMBOLS = (
     "hz_topo_params_planes", "hz_horizon_terrain_initialise_planes",
     "hz_horizon_terrain_sw_dir_cor_coarse", "hz_horizon_terrain_refraction", "hz_horizon_terrain_sun_times",
     "hz_hori_quantise", "hz_hori_dequantise", "hz_horizon_gridded_q16", "hz_horizon_gridded_scene_q16",
-    "hz_horizon_terrain_initialise_q16",
+    "hz_horizon_terrain_initialise_q16", "hz_topo_params_q16",
     "hz_horizon_distance", "hz_horizon_distance_scene", "hz_horizon_gridded_dist", "hz_horizon_gridded_scene_dist",
 )
 # hori_kind of the horizon-distance calls: the layout and the element type of `hori`, or'ed
@@ -184,6 +184,7 @@ def lib():
     L.hz_hori_to_planes.argtypes = [vp, ip, ip, ip, vp, ip]
     L.hz_hori_from_planes.argtypes = [vp, ip, ip, ip, vp, ip]
     L.hz_topo_params_planes.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp, vp, ip]
+    L.hz_topo_params_q16.argtypes = [vp, vp, ip, vp, ip, ip, ip, vp, vp, vp, ip]      # `int planes` follows hori_q
     L.hz_horizon_locations.argtypes = [
         vp, ip, ip, vp, vp, vp, vp, vp, ip, ip, C.c_float, C.c_float, C.c_char_p, C.c_char_p,
         C.c_float, vp, ip, C.POINTER(hz_opts), C.POINTER(hz_stats)]

@@ -313,7 +313,8 @@ int hz_hori_quantise(const float *src, size_t n, uint16_t *dst, int device) { re
 int hz_hori_dequantise(const uint16_t *src, size_t n, float *dst, int device) { return q16_convert(false, src, n, dst, device); }
 
 // ---------------------------------------------------------------------------------------
-// the reductions over the azimuth axis (hz_topo.hip): three single-output entry points, hz_topo_params, hz_topo_params_planes
+// the reductions over the azimuth axis (hz_topo.hip): three single-output entry points, hz_topo_params, hz_topo_params_planes,
+// hz_topo_params_q16
 // ---------------------------------------------------------------------------------------
 // The planes form: rows [rb, re) of every plane back into a bounded cell-major buffer (k_planes_to_hori), then the
 // reduction launch the cell-major form makes on it -- no numerics are written again, so every map is the same words.
@@ -345,30 +346,65 @@ static int topo_launch_planes(const float *azim, const float *planes, const floa
     return HZ_OK;
 }
 
-// The one driver of the five entry points.  `planes`: hori is planes[azim][y][x] (host or device), else cell-major.
-// `no_output`: the message when no output is asked for (a single-output entry point hands its one output in its slot).
-static int topo_api(bool planes, const char *no_output, const float *azim, const float *hori, const float *vec_tilt, int len_0,
-                    int len_1, int len_2, float *svf, float *vsf, float *openness, int device) {
+// The direct planes form (codes always; float planes under hz_debug_set("topo_planes_direct", 1)): k_topo_planes reads the
+// planes as they lie, one lane per cell -- no cell-major buffer and no second pass.  Device planes are one launch; host
+// planes go through the row-slab staging above at the element's size.
+static std::atomic<int> g_topo_planes_direct{0};
+static int topo_launch_planes_direct_staged(const float *azim, const void *planes, bool q16, const float *tilt, int len_0, int len_1,
+                                            int len_2, float *svf, float *vsf, float *openness, hipStream_t st) {
+    const size_t ncell = (size_t)len_0 * len_1, A = (size_t)len_2, elem = q16 ? sizeof(uint16_t) : sizeof(float);
+    if (is_device_ptr(planes)) return topo_launch_planes_direct(azim, planes, q16, ncell, tilt, ncell, len_2, svf, vsf, openness, st);
+    const int rows = (int)std::max<size_t>(1, planes_chunk_cells(ncell, len_2) / (size_t)len_1);
+    const size_t chunk = (size_t)rows * len_1;
+    DevBuf d_p;
+    HZ_HIP(d_p.alloc(chunk * A * elem));
+    for (int rb = 0; rb < len_0; rb += rows) {
+        const int re = std::min(rb + rows, len_0);
+        const size_t c0 = (size_t)rb * len_1, n = (size_t)(re - rb) * len_1;
+        HZ_HIP(hipMemcpy2DAsync(d_p.p, n * elem, static_cast<const char *>(planes) + c0 * elem, ncell * elem, n * elem, A,
+                                hipMemcpyHostToDevice, st));
+        const int rc = topo_launch_planes_direct(azim, d_p.p, q16, n, tilt ? tilt + 3 * c0 : nullptr, n, len_2, svf ? svf + c0 : nullptr,
+                                                 vsf ? vsf + c0 : nullptr, openness ? openness + c0 : nullptr, st);
+        if (rc) { (void)hipStreamSynchronize(st); return rc; }
+        HZ_HIP(hipStreamSynchronize(st));           // the chunk buffer is used again
+    }
+    return HZ_OK;
+}
+
+// The one driver of the six entry points.  `planes`: hori is planes[azim][y][x] (host or device), else cell-major; `q16`: its
+// elements are 16-bit codes, else float32.  `no_output`: the message when no output is asked for (a single-output entry
+// point hands its one output in its slot).
+static int topo_api(bool planes, bool q16, const char *no_output, const float *azim, const void *hori, const float *vec_tilt,
+                    int len_0, int len_1, int len_2, float *svf, float *vsf, float *openness, int device) {
     const bool tilt = svf || vsf;
     if (!svf && !vsf && !openness) return set_error(HZ_ERR_ARG, "%s", no_output);
     if (!azim || !hori || (tilt && !vec_tilt)) return set_error(HZ_ERR_ARG, "NULL argument");
+    if (q16 && (reinterpret_cast<uintptr_t>(hori) & (sizeof(uint16_t) - 1)))
+        return set_error(HZ_ERR_ARG, "an array is not aligned to its element type");
     // (the openness reads no azim[1] - azim[0]: one azimuth is enough, as in the reference)
     if (len_0 <= 0 || len_1 <= 0 || len_2 < (tilt ? 2 : 1)) return set_error(HZ_ERR_ARG, "Inconsistent/incorrect shapes of input arrays");
     int rc;
-    if (planes && (rc = planes_check_shape(azim, hori, len_0, len_1, len_2))) return rc;
+    if ((planes || q16) && (rc = planes_check_shape(azim, hori, len_0, len_1, len_2))) return rc;
     if ((rc = select_device(device))) return rc;
     hipStream_t st = nullptr;
     const size_t ncell = (size_t)len_0 * len_1;
-    DevIn<float> d_azim, d_hori, d_tilt;
+    DevIn<float> d_azim, d_tilt;
+    DevIn<unsigned char> d_hori;                     // cell-major only: planes are staged by their route
     DevOut<float> d_svf, d_vsf, d_open;
     if ((rc = d_azim.bind(azim, (size_t)len_2, st))) return rc;
-    if (!planes) if ((rc = d_hori.bind(hori, ncell * (size_t)len_2, st))) return rc;
+    if (!planes) if ((rc = d_hori.bind(static_cast<const unsigned char *>(hori), ncell * (size_t)len_2 * (q16 ? sizeof(uint16_t) : sizeof(float)), st))) return rc;
     if (tilt) if ((rc = d_tilt.bind(vec_tilt, ncell * 3, st))) return rc;
     if ((rc = d_svf.bind(svf, svf ? ncell : 0))) return rc;
     if ((rc = d_vsf.bind(vsf, vsf ? ncell : 0))) return rc;
     if ((rc = d_open.bind(openness, openness ? ncell : 0))) return rc;
-    rc = planes ? topo_launch_planes(d_azim.dev, hori, d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st)
-                : topo_launch(d_azim.dev, d_hori.dev, d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st);
+    if (planes && (q16 || g_topo_planes_direct.load(std::memory_order_relaxed)))
+        rc = topo_launch_planes_direct_staged(d_azim.dev, hori, q16, d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st);
+    else if (planes)
+        rc = topo_launch_planes(d_azim.dev, static_cast<const float *>(hori), d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st);
+    else if (q16)
+        rc = topo_launch_q16(d_azim.dev, reinterpret_cast<const uint16_t *>(d_hori.dev), d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st);
+    else
+        rc = topo_launch(d_azim.dev, reinterpret_cast<const float *>(d_hori.dev), d_tilt.dev, len_0, len_1, len_2, d_svf.dev, d_vsf.dev, d_open.dev, st);
     if (rc) return rc;
     if ((rc = d_svf.finish(st)) || (rc = d_vsf.finish(st)) || (rc = d_open.finish(st))) return rc;
     HZ_HIP(hipStreamSynchronize(st));
@@ -379,23 +415,28 @@ static const char *const TOPO_NO_OUTPUT = "no output requested (svf, vsf and ope
 
 int hz_sky_view_factor(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
                        int len_2, float *svf, int device) {
-    return topo_api(false, "NULL argument", azim, hori, vec_tilt, len_0, len_1, len_2, svf, nullptr, nullptr, device);
+    return topo_api(false, false, "NULL argument", azim, hori, vec_tilt, len_0, len_1, len_2, svf, nullptr, nullptr, device);
 }
 int hz_visible_sky_fraction(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1,
                             int len_2, float *vsf, int device) {
-    return topo_api(false, "NULL argument", azim, hori, vec_tilt, len_0, len_1, len_2, nullptr, vsf, nullptr, device);
+    return topo_api(false, false, "NULL argument", azim, hori, vec_tilt, len_0, len_1, len_2, nullptr, vsf, nullptr, device);
 }
 int hz_topographic_openness(const float *azim, const float *hori, int len_0, int len_1, int len_2, float *top,
                             int device) {
-    return topo_api(false, "NULL argument", azim, hori, nullptr, len_0, len_1, len_2, nullptr, nullptr, top, device);
+    return topo_api(false, false, "NULL argument", azim, hori, nullptr, len_0, len_1, len_2, nullptr, nullptr, top, device);
 }
 int hz_topo_params(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
                    float *svf, float *vsf, float *openness, int device) {
-    return topo_api(false, TOPO_NO_OUTPUT, azim, hori, vec_tilt, len_0, len_1, len_2, svf, vsf, openness, device);
+    return topo_api(false, false, TOPO_NO_OUTPUT, azim, hori, vec_tilt, len_0, len_1, len_2, svf, vsf, openness, device);
 }
 int hz_topo_params_planes(const float *azim, const float *planes, const float *vec_tilt, int len_0, int len_1, int len_2,
                           float *svf, float *vsf, float *openness, int device) {
-    return topo_api(true, TOPO_NO_OUTPUT, azim, planes, vec_tilt, len_0, len_1, len_2, svf, vsf, openness, device);
+    return topo_api(true, false, TOPO_NO_OUTPUT, azim, planes, vec_tilt, len_0, len_1, len_2, svf, vsf, openness, device);
+}
+int hz_topo_params_q16(const float *azim, const uint16_t *hori_q, int planes, const float *vec_tilt, int len_0, int len_1, int len_2,
+                       float *svf, float *vsf, float *openness, int device) {
+    if (planes != 0 && planes != 1) return set_error(HZ_ERR_ARG, "planes must be 0 or 1");
+    return topo_api(planes != 0, true, TOPO_NO_OUTPUT, azim, hori_q, vec_tilt, len_0, len_1, len_2, svf, vsf, openness, device);
 }
 
 
@@ -461,6 +502,7 @@ int hz_debug_set(const char *key, int value) {
     else if (!strcmp(key, "horisun_chunk")) hz::g_horisun_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_coarse_tile")) hz::g_horisun_coarse_tile.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horisun_coarse_route")) hz::g_horisun_coarse_route.store(value < 0 ? -1 : (value == 1 ? 1 : 0), std::memory_order_relaxed);
+    else if (!strcmp(key, "topo_planes_direct")) g_topo_planes_direct.store(value > 0, std::memory_order_relaxed);
     else if (!strcmp(key, "planes_chunk")) g_planes_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "q16_chunk")) g_q16_chunk.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else if (!strcmp(key, "horidist_traversal")) {    // (< 0: the default; results never depend on it)

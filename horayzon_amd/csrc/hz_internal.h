@@ -291,6 +291,13 @@ int horizon_num_blocks(const HorizonArgs &a);
 // not NULL are written (at least one; vec_tilt is read when svf or vsf is)
 int topo_launch(const float *azim, const float *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
                 float *svf, float *vsf, float *openness, hipStream_t st);
+// the same on cell-major 16-bit codes, and straight from an azimuth-major horizon of either element type (q16: codes):
+// `planes` points at azimuth 0 of the first of `ncell` cells, azimuth k lies k * stride elements on, vec_tilt and the maps
+// start at that cell.  Every map is the words topo_launch gives on the decoded, cell-major horizon.
+int topo_launch_q16(const float *azim, const uint16_t *hori, const float *vec_tilt, int len_0, int len_1, int len_2,
+                    float *svf, float *vsf, float *openness, hipStream_t st);
+int topo_launch_planes_direct(const float *azim, const void *planes, bool q16, size_t stride, const float *vec_tilt, size_t ncell,
+                              int A, float *svf, float *vsf, float *openness, hipStream_t st);
 
 // hz_near.hip: near-field certificates (pre-pass of the horizon kernel)
 struct NearArgs {

@@ -302,6 +302,18 @@ int hz_topo_params_planes(const float *azim, const float *planes, const float *v
 /* ("q16_chunk" elements).  n == 0 succeeds.                                                                      */
 int hz_hori_quantise(const float *src, size_t n, uint16_t *dst, int device);
 int hz_hori_dequantise(const uint16_t *src, size_t n, float *dst, int device);
+/* hz_topo_params / hz_topo_params_planes on codes (clause 17): planes = 0: hori_q is          */
+/* u16[len_0][len_1][len_2], planes = 1: u16[len_2][len_0][len_1].  Every pointer is host or device memory, hori_q  */
+/* aligned to 2 bytes (a view at an odd element is fine); any non-empty subset of svf / vsf / openness.  A code is  */
+/* decoded to float32 first and the float kernels' operation sequence runs on that float32: each map is, word for   */
+/* word, the map hz_topo_params returns on decode(hori_q); 0xFFFF behaves as a NaN horizon does (svf and vsf take   */
+/* the tilted plane's own horizon and stay numbers, openness becomes NaN).  No float32 copy of the horizon is made: */
+/* cell-major codes are read by the tiled kernel, planes of codes -- one lane per cell, coalesced as they lie -- by */
+/* the direct kernel; host planes are staged in row slabs ("planes_chunk").  Checks and messages as hz_topo_params, */
+/* plus "planes must be 0 or 1" and "an array is not aligned to its element type".                                  */
+int hz_topo_params_q16(const float *azim, const uint16_t *hori_q, int planes, const float *vec_tilt,
+                       int len_0, int len_1, int len_2,
+                       float *svf, float *vsf, float *openness, int device);
 /* hz_horizon_gridded_planes / _scene_planes with `hori_q` in place of hori_planes (host or device memory):       */
 /* planes = 0: u16[rows][dim_in_1][azim_num], planes = 1: u16[azim_num][rows][dim_in_1].  Each chunk of rows is    */
 /* traced into the bounded float32 chunk buffer, reduced there -- opts->svf and topo come from the unquantised     */
@@ -475,6 +487,8 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* tile take the kernel without LDS), "horisun_chunk" = sun positions per launch of hz_horizon_terrain_run (<= 0: the default), */
 /* "horisun_coarse_route" / "horisun_coarse_tile": see hz_horizon_terrain_sw_dir_cor_coarse (< 0: the default),                 */
 /* "planes_chunk" = cells per staging chunk of hz_hori_to_planes / _from_planes / hz_topo_params_planes (<= 0: the default),   */
+/* "topo_planes_direct" = 1: hz_topo_params_planes reduces float32 planes with the direct one-lane-per-cell kernel that planes */
+/* of codes always take, not by transposing row slabs back (0 or < 0: the default; the maps are the same words either way),   */
 /* "q16_chunk" = elements per staging chunk of hz_hori_quantise / hz_hori_dequantise (<= 0: the default),                        */
 /* "leaf_lend" = 0: the horizon kernel's fast stack runs without leaf lending (1 or < 0: the default, with it)                  */
 /* "flat_refill" = 0: guess_constant's refill runs the search state machine's if-chain (1 or < 0: the default, the branch-free */
