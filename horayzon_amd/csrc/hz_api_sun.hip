@@ -2,8 +2,8 @@
 // Terrain (hz_terrain_*: rays against the scene, restating CppTerrain, shadow_comp.cpp:304-605) and HorizonTerrain
 // (hz_horizon_terrain_*: look-ups in a stored horizon).
 //
-// Six calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
-// hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
+// Seven calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
+// hz_terrain_viewshed, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
 // allocations, one chunk loop with the launches, finish; what they share -- device, lock, stream, timers, the scratch tally,
 // staged inputs, staged outputs -- is SunCall and ChunkFeed below.
 #include "hz_internal.h"
@@ -370,6 +370,20 @@ static void terrain_stats(const Terrain *t, const unsigned long long *cnt, hz_st
     stats->bvh_height = t->scene->hdr.height; stats->scene_bytes = t->scene->hdr.total_bytes;
 }
 
+// host positions (chunks of k) go up through the handle's own buffer: no allocation per call
+static int terrain_stage_positions(Terrain *t, ChunkFeed<float> &suns, int k) {
+    if (!suns.staged()) return HZ_OK;
+    if (t->sun_cap < 3 * (size_t)k) {
+        if (t->sun_dev) (void)hipFree(t->sun_dev);
+        t->sun_dev = nullptr; t->sun_cap = 0;
+        const size_t cap = std::max<size_t>(3 * (size_t)k, 3 * 256);
+        HZ_HIP(hipMalloc((void **)&t->sun_dev, cap * sizeof(float)));
+        t->sun_cap = cap;
+    }
+    suns.stage = t->sun_dev;
+    return HZ_OK;
+}
+
 static int terrain_run(Terrain *t, const float *sun_positions, int num_sun, int which, uint8_t *out_u8,
                        float *out_f32, hz_stats *stats) {
     if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "Terrain is not initialised");
@@ -381,16 +395,7 @@ static int terrain_run(Terrain *t, const float *sun_positions, int num_sun, int 
     const size_t nc = (size_t)t->dim_in_0 * t->dim_in_1;
     const int k = std::min(num_sun, HZ_SHADOW_MAX_POS);
     ChunkFeed<float> suns(sun_positions, 3);
-    if (suns.staged()) {                          // host positions go up through the handle's own buffer: no allocation per call
-        if (t->sun_cap < 3 * (size_t)k) {
-            if (t->sun_dev) (void)hipFree(t->sun_dev);
-            t->sun_dev = nullptr; t->sun_cap = 0;
-            const size_t cap = std::max<size_t>(3 * (size_t)k, 3 * 256);
-            HZ_HIP(hipMalloc((void **)&t->sun_dev, cap * sizeof(float)));
-            t->sun_cap = cap;
-        }
-        suns.stage = t->sun_dev;
-    }
+    if ((rc = terrain_stage_positions(t, suns, k))) return rc;
     DevOut<uint8_t> d_u8; DevOut<float> d_f32;
     if ((rc = call.bind(d_u8, out_u8, nc * (size_t)num_sun, false))) return rc;
     if ((rc = call.bind(d_f32, out_f32, nc * (size_t)num_sun, false))) return rc;
@@ -542,6 +547,57 @@ int hz_terrain_sw_dir_cor_coarse(hz_terrain *terrain, const float *sun_positions
     unsigned long long cnt[HZ_SHADOW_CNT_N];
     if ((rc = terrain_end(t, call, cnt))) return rc;
     if ((rc = call.finish(stats, d_sw, d_lit))) return rc;
+    terrain_stats(t, cnt, stats);
+    if (stats) stats->scratch_bytes = call.scratch;
+    return HZ_OK;
+}
+
+// Terrain.viewshed (hz_viewshed.hip: k_viewshed_refill; DESIGN.md section 4 clause 18).  Observers go in launches of up to
+// HZ_SHADOW_MAX_POS (grid.y), as the positions of terrain_run do.  The kernel writes the codes and adds to the two counts
+// itself: no scratch per chunk, and device memory besides the outputs -- the handle's staging buffer for host observers,
+// outputs given as host pointers staged on the device -- does not depend on num_obs but for those staged outputs.
+int hz_terrain_viewshed(hz_terrain *terrain, const float *observers, int num_obs, float target_elev, float max_dist, int facing,
+                        uint8_t *visible, int32_t *seen_count, int64_t *cells_seen, hz_stats *stats) {
+    Terrain *t = reinterpret_cast<Terrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "Terrain is not initialised");
+    if (!observers || num_obs <= 0) return set_error(HZ_ERR_ARG, "array 'observers' has incorrect shape");
+    if (!visible && !seen_count && !cells_seen) return set_error(HZ_ERR_ARG, "no output buffer (visible, seen_count and cells_seen are NULL)");
+    const void *outs[3] = {visible, seen_count, cells_seen};
+    int rc;
+    if ((rc = check_distinct_outputs(outs, 3))) return rc;
+    if (!(target_elev >= 0.005f) || !std::isfinite(target_elev)) return set_error(HZ_ERR_ARG, "'target_elev' must be at least 0.005 m");
+    SunCall call;
+    if ((rc = call.start(t->device, t->scene->run_mu, t->stream))) return rc;
+    const size_t nc = (size_t)t->dim_in_0 * t->dim_in_1;
+    const int k = std::min(num_obs, HZ_SHADOW_MAX_POS);
+    ChunkFeed<float> obs(observers, 3);
+    if ((rc = terrain_stage_positions(t, obs, k))) return rc;
+    DevOut<uint8_t> d_vis; DevOut<int32_t> d_seen; DevOut<int64_t> d_cells;
+    if ((rc = call.bind(d_vis, visible, nc * (size_t)num_obs, false)) || (rc = call.bind(d_seen, seen_count, nc, true)) ||
+        (rc = call.bind(d_cells, cells_seen, (size_t)num_obs, false)))
+        return rc;
+    ShadowArgs a = terrain_args(t, 0);
+    a.refrac_cor = 0; a.refrac_fac = nullptr;     // a line of sight is not bent
+    ViewshedArgs v;
+    v.target_elev = target_elev; v.facing = facing ? 1 : 0;
+    v.has_max = (max_dist > 0.0f && std::isfinite(max_dist)) ? 1 : 0;
+    v.max_dist = v.has_max ? max_dist : 0.0f;
+    v.seen_count = d_seen.dev;
+    if (d_seen.dev) HZ_HIP(hipMemsetAsync(d_seen.dev, 0, nc * sizeof(int32_t), call.st));
+    if (d_cells.dev) HZ_HIP(hipMemsetAsync(d_cells.dev, 0, (size_t)num_obs * sizeof(int64_t), call.st));
+    if ((rc = terrain_begin(t, call))) return rc;
+    a.out_f32 = nullptr;
+    for (int s0 = 0; s0 < num_obs; s0 += k) {
+        a.num_sun = std::min(k, num_obs - s0);
+        if ((rc = obs.at(s0, a.num_sun, call.st, &a.suns))) return rc;
+        a.out_u8 = d_vis.dev ? d_vis.dev + nc * (size_t)s0 : nullptr;
+        v.cells_seen = d_cells.dev ? d_cells.dev + s0 : nullptr;
+        if ((rc = viewshed_launch(t->scene, a, v, call.st))) return rc;
+    }
+    if ((rc = viewshed_masked_launch(a.mask, nc, d_seen.dev, call.st))) return rc;
+    unsigned long long cnt[HZ_SHADOW_CNT_N];
+    if ((rc = terrain_end(t, call, cnt))) return rc;
+    if ((rc = call.finish(stats, d_vis, d_seen, d_cells))) return rc;
     terrain_stats(t, cnt, stats);
     if (stats) stats->scratch_bytes = call.scratch;
     return HZ_OK;

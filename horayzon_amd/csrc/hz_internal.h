@@ -361,6 +361,20 @@ int accum_add_launch(const uint8_t *codes, const float *vals, size_t n, int k, c
 int accum_final_launch(const uint8_t *mask, size_t n, float fill, const double *acc_sw, const double *acc_lit, float *out_sw,
                        float *out_lit, hipStream_t st);
 
+// hz_viewshed.hip (hz_terrain_viewshed; device pointers; DESIGN.md section 4, clause 18): one launch of k_viewshed_refill over
+// the a.num_sun observers a.suns of a chunk.  Of `a` the inputs, suns, num_sun, out_u8 (the codes u8[num_sun][cells], or null),
+// count_work and counters are read.  seen_count i32[cells] (null: not wanted) takes +1 per observer that sees the cell,
+// cells_seen i64[num_sun] (null: not wanted) + the cells each observer sees: the caller zeroes both, and sets the masked
+// cells of seen_count to -1 after the last launch (viewshed_masked_launch).
+struct ViewshedArgs {
+    float target_elev, max_dist;
+    int has_max, facing;                 // has_max = 0: no distance limit (max_dist is not read)
+    int32_t *seen_count;
+    int64_t *cells_seen;
+};
+int viewshed_launch(const Scene *sc, const ShadowArgs &a, const ViewshedArgs &v, hipStream_t st);
+int viewshed_masked_launch(const uint8_t *mask, size_t n, int32_t *seen_count, hipStream_t st);
+
 // hz_subgrid.hip (hz_terrain_sw_dir_cor_coarse; device pointers): n u32[dim_0 / p0][dim_1 / p1] = unmasked cells per coarse
 // cell; one chunk of k positions of accumulate's scratch (codes and / or vals, [k][cells]) reduced to block means
 // f_cor / lit f32[k][gy][gx] (null: not wanted; f_cor needs vals, lit needs codes), coarse cells without a cell = fill

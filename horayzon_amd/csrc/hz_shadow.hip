@@ -6,34 +6,13 @@
 // shadow_comp.cpp:430-446).  Same tile / XCD mapping and LDS staging as the horizon
 // kernel; the BVH is persistent in the Terrain handle (built once, :318-380).
 #include "hz_internal.h"
+#include "hz_shadow.h"
 #include "hz_crmath.h"
 #include <cstdlib>
 
 namespace hz {
 
 #define HZ_TPB 256
-#ifndef HZ_SHADOW_LEAF_BIAS
-#define HZ_SHADOW_LEAF_BIAS 24   // node step when 16 * n_node >= bias * n_leaf (hz_trace); 20 until round 4 (profiles/r04/shadow_leaf_bias.log)
-#endif
-
-struct ShadowParams {
-    SceneView sv;
-    const float *vec_tilt, *vec_norm, *surf_enl_fac, *elevation;
-    const uint8_t *mask;
-    int offset_0, offset_1, dim_in_0, dim_in_1;
-    TileMap tm;
-    const float *suns;       // device f32[num_sun][3]; blockIdx.y selects the position
-    size_t out_stride;       // cells per sun position (outputs of position s start at s * out_stride)
-    float fill, dot_prod_min;
-    int refrac, which;
-    const double *refrac_fac;   // refrac: per cell ((double)pressure / 101.0) * (283.0 / (273.0 + (double)temperature_degC)), k_refrac_factor
-    uint8_t *out_u8; float *out_f32;
-    int top_nodes, stack_bytes;
-    int stack_cap;                 // FAST: entries of the fast stack (hz_trace, !LEVELSTACK), sentinel included
-    int nb;                  // k_shadow_refill: 8 x 8 blocks per wave
-    unsigned long long *counters;
-};
-
 // The float libm calls of the reference's refraction branch (acos / tan / pow / cos / sin on float arguments
 // resolve to the float overloads, shadow_comp.cpp:19): self-contained correctly rounded versions shared with
 // the CPU oracle (hz_crmath.h): with refraction, shadow codes and sw_dir_cor are bit-identical TO THAT CONTRACT (the
@@ -52,12 +31,6 @@ __device__ __forceinline__ float deg2rad_f(float a) {
 }
 __device__ __forceinline__ float rad2deg_f(float a) {
     return (float)(hz_crm_div_const((double)a, 3.14159265358979323846, 1.0 / 3.14159265358979323846) * 180.0);
-}
-
-// shadow_comp.cpp:96-106
-__device__ __forceinline__ void vec_unit(float &x, float &y, float &z) {
-    const float mag = __builtin_sqrtf((x * x + y * y) + z * z);
-    x = x / mag; y = y / mag; z = z / mag;
 }
 
 // shadow_comp.cpp:135-159 (Saemundsson), float/double promotions as there.  `fac` = the factor that depends on the cell's
@@ -90,24 +63,6 @@ int shadow_refrac_factor(const float *elevation, size_t n, double *out, hipStrea
     hipLaunchKernelGGL(k_refrac_factor, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, elevation, n, out);
     HZ_HIP(hipGetLastError());
     return HZ_OK;
-}
-
-// any-hit traversal to completion (regroup = 0: never suspends; no LDS nodelet: top = null)
-template <bool COUNT>
-__device__ __forceinline__ void shadow_counters(const ShadowParams &p, unsigned rays, const TravCounters &tc, int lane) {
-    unsigned long long r = rays;
-    for (int off = 32; off > 0; off >>= 1) r += __shfl_xor(r, off);
-    if (lane == 0 && r) atomicAdd(&p.counters[HZ_SHADOW_CNT_RAYS], r);
-    if (COUNT) {
-        unsigned long long nc = tc.nodes, tn = tc.tris, wn = tc.w_nodes, wl = tc.w_leaves;
-        for (int off = 32; off > 0; off >>= 1) {
-            nc += __shfl_xor(nc, off); tn += __shfl_xor(tn, off); wn += __shfl_xor(wn, off); wl += __shfl_xor(wl, off);
-        }
-        if (lane == 0) {
-            atomicAdd(&p.counters[HZ_SHADOW_CNT_NODES], nc); atomicAdd(&p.counters[HZ_SHADOW_CNT_TRIS], tn);
-            atomicAdd(&p.counters[HZ_SHADOW_CNT_WAVE_NODE], wn); atomicAdd(&p.counters[HZ_SHADOW_CNT_WAVE_LEAF], wl);
-        }
-    }
 }
 
 // Per-cell set-up shared by both kernels: classification without a ray (masked / self-shaded / outside ang_max) is
@@ -192,19 +147,9 @@ __device__ __forceinline__ void shadow_result(const ShadowParams &p, size_t cell
 #ifndef HZ_SHADOW_FAST_CAP_DEFAULT
 #define HZ_SHADOW_FAST_CAP_DEFAULT 19   // 21 KiB of LDS per workgroup: 7 resident; round 4: level stack 1.074 -> fast stack 0.964 ms per position at 5 workgroups (profiles/r04/ab_shadow_fast_stack.log)
 #endif
-#ifndef HZ_SHADOW_REGROUP
-#define HZ_SHADOW_REGROUP 16      // refill when fewer lanes than this are still traversing (40 until round 5; re-swept 40 ... 8 after the loop rewrite:
-                                  // 16 - 20 is the flat optimum, -0.5 % without and -7.7 % with refraction, profiles/r05/ab_shadow_and_locations_thresholds.log)
-#endif
 // FAST: the fast stack discipline of hz_trace (every pending sibling its own entry, written for the fewest instructions;
 // `stack_cap` entries behind two padding rows).  A ray that runs out of entries is traced again, to completion, with the
 // one-entry-per-level discipline in the same LDS column of its lane (the launcher makes sure the tree's height fits).
-// resident workgroups per CU the register allocation is held to (profiles/r04/ab_shadow_fast_stack.log, ms per sun position:
-// unconstrained = 86 VGPRs = 5 workgroups 0.955; 6 (80 VGPRs, no spills) 0.884; 7 (72 VGPRs, 6 spilled) 0.857; 8 (64 VGPRs, 21
-// spilled) 0.957).  The counting instantiation carries ~10 more live values and is left at 5.
-#ifndef HZ_SHADOW_WG
-#define HZ_SHADOW_WG 7
-#endif
 // COUNT: also count node visits / triangle tests / wave-level steps (Terrain count_work; the roofline's B_trav)
 template <bool COUNT, bool FAST>
 __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SHADOW_WG) void k_shadow_refill(ShadowParams p) {
@@ -279,9 +224,8 @@ std::atomic<int> g_shadow_fast_cap{HZ_SHADOW_FAST_CAP_DEFAULT};      // hz_debug
 std::atomic<int> g_topo_wide{0};
 std::atomic<int> g_accum_chunk{0};
 
-// Launch configuration of the refill kernels (k_shadow_refill, k_accum_refill) for one launch of a.num_sun positions:
-// parameters, dynamic LDS, grid, and whether the fast stack is used.  Returns 0 when there is nothing to launch.
-static int shadow_config(const Scene *sc, const ShadowArgs &a, ShadowParams &p, size_t &lds, dim3 &grid, bool &fast) {
+// Launch configuration of the refill kernels (hz_shadow.h)
+int shadow_config(const Scene *sc, const ShadowArgs &a, ShadowParams &p, size_t &lds, dim3 &grid, bool &fast) {
     p.sv = scene_view(sc);
     p.vec_tilt = a.vec_tilt; p.vec_norm = a.vec_norm; p.surf_enl_fac = a.surf_enl_fac; p.elevation = a.elevation;
     p.mask = a.mask;

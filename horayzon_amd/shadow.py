@@ -310,6 +310,71 @@ class Terrain:
         _sw_dir_cor_coarse(self, "hz_terrain_sw_dir_cor_coarse", sun_positions, pixel_per_gc, f_cor, sunlit_frac)
 
 
+    # --- additive: line-of-sight maps from observer points ------------------------------------------------------------
+    def viewshed(self, observers, *, visible=None, seen_count=None, cells_seen=None,
+                 target_elev=0.05, max_dist=None, facing=True):
+        """Which cells have a free line of sight to each point of observers f32[S][3] (S >= 1; the scene's ENU frame, the
+        frame of ``sun_position``; NumPy or a torch tensor on the Terrain's GPU; finite): a mast, a camera, a candidate
+        site.  Unlike a sun position the observer ends the ray, so terrain behind it blocks nothing.  Per observer and
+        cell one code (clause 18) -- 0: in sight, 1: the tilted surface faces away (``facing``; no ray),
+        2: terrain in between, 3: masked, 4: farther than ``max_dist`` (no ray) -- for the point ``target_elev`` [m]
+        (>= 0.005) above the surface along ``vec_norm``; ``max_dist`` [m] is None or > 0; with ``facing=False`` back-facing
+        cells are traced too.  Refraction is never applied.  Outputs, any subset, at least one: ``visible`` u8[S][y][x] the
+        codes, ``seen_count`` i32[y][x] the number of observers that see the cell (masked cells: -1), ``cells_seen``
+        i64[S] the number of cells each observer sees; NumPy or torch tensors on the Terrain's GPU.
+        ``last_stats["num_rays"]`` is the number of rays traced.  ``last_stats["scratch_bytes"]``, the device memory the call
+        allocates besides the buffers, does not grow with S; NumPy observers also go through the Terrain's own staging
+        buffer (12 bytes per observer, at most 32768 observers at a time, kept with the object and not counted there).  The
+        finiteness check of observers given as a tensor is a reduction on the GPU whose result is read back: one device
+        synchronisation per call before the launches."""
+        outs = (("visible", visible, 3, np.uint8), ("seen_count", seen_count, 2, np.int32),
+                ("cells_seen", cells_seen, 1, np.int64))
+        self._array_arg(observers, 2, "observers")
+        for name, buf, ndim, dtype in outs:
+            if buf is not None:
+                self._array_arg(buf, ndim, name, dtype)
+
+        def number(v):
+            return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+        if not number(target_elev):
+            raise TypeError("Argument 'target_elev' has incorrect type (expected a number, got %s)" % type(target_elev).__name__)
+        if max_dist is not None and not number(max_dist):
+            raise TypeError("Argument 'max_dist' has incorrect type (expected a number or None, got %s)" % type(max_dist).__name__)
+        if not isinstance(facing, (bool, np.bool_)):
+            raise TypeError("Argument 'facing' has incorrect type (expected bool, got %s)" % type(facing).__name__)
+        given = [buf for _, buf, _, _ in outs if buf is not None]
+
+        def finite():
+            if _is_tensor(observers):
+                import torch
+                return bool(torch.isfinite(observers).all().item())
+            return bool(np.isfinite(observers).all())
+        V.run((
+            (ValueError, "at least one of 'visible', 'seen_count' and 'cells_seen' must be given", lambda: not given),
+            (ValueError, "array 'observers' has incorrect shape", lambda: observers.shape[1] != 3 or observers.shape[0] < 1),
+            (ValueError, "array 'visible' has incorrect shape",
+             lambda: visible is not None and visible.shape[0] != observers.shape[0]),
+            (ValueError, "array 'cells_seen' has incorrect shape",
+             lambda: cells_seen is not None and cells_seen.shape[0] != observers.shape[0]),
+            (ValueError, "not all input arrays are C-contiguous", lambda: not all(_contiguous(a) for a in [observers] + given)),
+            (ValueError, "'visible', 'seen_count' and 'cells_seen' must be different arrays",
+             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            (ValueError, "'target_elev' must be at least 0.005 m", lambda: not (np.isfinite(target_elev) and target_elev >= 0.005)),
+            (ValueError, "'max_dist' must be None or greater than 0", lambda: max_dist is not None and not np.float32(max_dist) > 0),
+            (ValueError, "array 'observers' has non-finite entries", lambda: not finite()),
+        ))
+        for name, buf in (("visible", visible), ("seen_count", seen_count)):
+            if buf is not None:
+                self._check_out(buf, name)
+        if self._shape is None:
+            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
+        st = hz_stats()
+        _lib.check(_lib.lib().hz_terrain_viewshed(
+            self._h, ptr(observers), observers.shape[0], float(target_elev), 0.0 if max_dist is None else float(max_dist),
+            int(bool(facing)), ptr(visible), ptr(seen_count), ptr(cells_seen), C.byref(st)))
+        self.last_stats = st.as_dict()
+
+
 def _is_tensor(a):
     return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
 

@@ -609,6 +609,23 @@ int hz_terrain_accumulate(hz_terrain *terrain, const float *sun_positions, const
 int hz_terrain_sw_dir_cor_coarse(hz_terrain *terrain, const float *sun_positions, int num_sun,
                                  int pixel_per_gc_0, int pixel_per_gc_1,
                                  float *f_cor, float *sunlit_frac, hz_stats *stats);
+/* additive: line-of-sight maps from observer points (DESIGN.md section 4 clause 18). observers f32[num_obs][3] are points of   */
+/* the scene's ENU frame (the frame of sun_position), num_obs >= 1.  For observer P and inner cell c, everything float32, every */
+/* multiply, add and divide rounded on its own, associated as in hz_terrain_shadow's set-up, in this order:                      */
+/*   mask[c] != 1 -> 3;  T = v + norm * target_elev (v = the DEM vertex of c), d = P - T, mag = sqrtf((dx dx + dy dy) + dz dz);  */
+/*   a limit is given and mag > max_dist -> 4 (no ray);  !(mag > 0) -> 0 (no ray);  u = d / mag;                                 */
+/*   facing and !((tilt_x u_x + tilt_y u_y) + tilt_z u_z > 0) -> 1 (no ray: the surface faces away);                             */
+/*   else one any-hit ray with origin T, direction u and tfar = mag: a hit -> 2, no hit -> 0.                                    */
+/* Refraction is never applied (a Terrain initialised with refrac_cor gives the same codes).  visible u8[num_obs][y][x] takes   */
+/* the codes, seen_count i32[y][x] the number of observers with code 0 for the cell (masked cells: -1), cells_seen              */
+/* i64[num_obs] the number of cells with code 0 per observer; NULL = not wanted (at least one; they must differ).  Every        */
+/* pointer may be host or device memory.  target_elev >= 0.005 [m]; max_dist [m]: <= 0, NaN or infinite = no limit.             */
+/* stats->num_rays = rays traced.  hz_stats.scratch_bytes = device memory the call allocates besides the caller's buffers: the  */
+/* staging of a host seen_count; it does not grow with num_obs.  Not counted there: the staging of a host visible / cells_seen  */
+/* (num_obs * cells bytes, num_obs * 8 bytes) and the handle's own staging buffer for host observers, which hz_terrain_shadow   */
+/* and the batch calls share: it is kept with the handle, 12 bytes per observer of one launch, at most 32768 * 12 bytes         */
+int hz_terrain_viewshed(hz_terrain *terrain, const float *observers, int num_obs, float target_elev, float max_dist,
+                        int facing, uint8_t *visible, int32_t *seen_count, int64_t *cells_seen, hz_stats *stats);
 /* additive: 1 = later shadow / sw_dir_cor calls run the counting instantiation and also fill   */
 /* hz_stats.nodes_visited / tris_tested / wave_*_iters (slower; for the roofline's B_trav)      */
 int hz_terrain_count_work(hz_terrain *terrain, int on);
