@@ -2,8 +2,8 @@
 // Terrain (hz_terrain_*: rays against the scene, restating CppTerrain, shadow_comp.cpp:304-605) and HorizonTerrain
 // (hz_horizon_terrain_*: look-ups in a stored horizon).
 //
-// Seven calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
-// hz_terrain_viewshed, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
+// Eight calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
+// hz_terrain_viewshed, hz_terrain_sight_height, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
 // allocations, one chunk loop with the launches, finish; what they share -- device, lock, stream, timers, the scratch tally,
 // staged inputs, staged outputs -- is SunCall and ChunkFeed below.
 #include "hz_internal.h"
@@ -598,6 +598,77 @@ int hz_terrain_viewshed(hz_terrain *terrain, const float *observers, int num_obs
     unsigned long long cnt[HZ_SHADOW_CNT_N];
     if ((rc = terrain_end(t, call, cnt))) return rc;
     if ((rc = call.finish(stats, d_vis, d_seen, d_cells))) return rc;
+    terrain_stats(t, cnt, stats);
+    if (stats) stats->scratch_bytes = call.scratch;
+    return HZ_OK;
+}
+
+// the rules of sight_height's table (DESIGN.md section 4 clause 19): the kernel indexes it and does no arithmetic on it
+static int check_sight_heights(const float *h, int n) {
+    if (!(h[0] >= 0.005f)) return set_error(HZ_ERR_ARG, "'heights' must start at 0.005 m or above");
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(h[i])) return set_error(HZ_ERR_ARG, "'heights' has non-finite entries");
+    for (int i = 1; i < n; i++)
+        if (!(h[i] > h[i - 1])) return set_error(HZ_ERR_ARG, "'heights' must be strictly increasing");
+    return HZ_OK;
+}
+
+// Terrain.sight_height (hz_sight.hip: k_sight_refill; DESIGN.md section 4 clause 19).  Observers go in launches of up to
+// HZ_SHADOW_MAX_POS (grid.y), as in hz_terrain_viewshed.  The kernel writes the heights, takes the minimum over observers and
+// adds to the count itself: no scratch per chunk.  Device memory besides the outputs: the table if it came from the host
+// (4 bytes per entry, counted), a host `lowest` staged on the device (counted), the handle's staging buffer for host
+// observers and the staging of a host `height` / `cells_reached` (not counted, as in hz_terrain_viewshed).
+int hz_terrain_sight_height(hz_terrain *terrain, const float *observers, int num_obs, const float *heights, int num_heights,
+                            float max_dist, float *height, float *lowest, int64_t *cells_reached, hz_stats *stats) {
+    Terrain *t = reinterpret_cast<Terrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "Terrain is not initialised");
+    if (!observers || num_obs <= 0) return set_error(HZ_ERR_ARG, "array 'observers' has incorrect shape");
+    if (!heights || num_heights < 1 || num_heights > 65535)
+        return set_error(HZ_ERR_ARG, "array 'heights' must have 1 to 65535 entries");
+    if (!height && !lowest && !cells_reached) return set_error(HZ_ERR_ARG, "no output buffer (height, lowest and cells_reached are NULL)");
+    const void *outs[3] = {height, lowest, cells_reached};
+    int rc;
+    if ((rc = check_distinct_outputs(outs, 3))) return rc;
+    ChunkFeed<float> table(heights, 1);
+    if (table.staged() && (rc = check_sight_heights(heights, num_heights))) return rc;
+    SunCall call;
+    if ((rc = call.start(t->device, t->scene->run_mu, t->stream))) return rc;
+    if (!table.staged()) {                        // a table in device memory is read back for its checks
+        std::vector<float> h((size_t)num_heights);
+        HZ_HIP(hipMemcpy(h.data(), heights, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if ((rc = check_sight_heights(h.data(), num_heights))) return rc;
+    }
+    const size_t nc = (size_t)t->dim_in_0 * t->dim_in_1;
+    const int k = std::min(num_obs, HZ_SHADOW_MAX_POS);
+    ChunkFeed<float> obs(observers, 3);
+    if ((rc = terrain_stage_positions(t, obs, k))) return rc;
+    SightArgs v;
+    if ((rc = call.stage(num_heights, table)) || (rc = table.at(0, num_heights, call.st, &v.heights))) return rc;   // staged once
+    DevOut<float> d_height, d_lowest; DevOut<int64_t> d_cells;
+    if ((rc = call.bind(d_height, height, nc * (size_t)num_obs, false)) || (rc = call.bind(d_lowest, lowest, nc, true)) ||
+        (rc = call.bind(d_cells, cells_reached, (size_t)num_obs, false)))
+        return rc;
+    ShadowArgs a = terrain_args(t, 1);
+    a.refrac_cor = 0; a.refrac_fac = nullptr;     // a line of sight is not bent
+    v.num_heights = num_heights;
+    v.has_max = (max_dist > 0.0f && std::isfinite(max_dist)) ? 1 : 0;
+    v.max_dist = v.has_max ? max_dist : 0.0f;
+    v.lowest = d_lowest.dev;
+    if ((rc = sight_lowest_init_launch(nc, d_lowest.dev, call.st))) return rc;
+    if (d_cells.dev) HZ_HIP(hipMemsetAsync(d_cells.dev, 0, (size_t)num_obs * sizeof(int64_t), call.st));
+    if ((rc = terrain_begin(t, call))) return rc;
+    a.out_u8 = nullptr;
+    for (int s0 = 0; s0 < num_obs; s0 += k) {
+        a.num_sun = std::min(k, num_obs - s0);
+        if ((rc = obs.at(s0, a.num_sun, call.st, &a.suns))) return rc;
+        a.out_f32 = d_height.dev ? d_height.dev + nc * (size_t)s0 : nullptr;
+        v.cells_reached = d_cells.dev ? d_cells.dev + s0 : nullptr;
+        if ((rc = sight_launch(t->scene, a, v, call.st))) return rc;
+    }
+    if ((rc = sight_masked_launch(a.mask, nc, d_lowest.dev, call.st))) return rc;
+    unsigned long long cnt[HZ_SHADOW_CNT_N];
+    if ((rc = terrain_end(t, call, cnt))) return rc;
+    if ((rc = call.finish(stats, d_height, d_lowest, d_cells))) return rc;
     terrain_stats(t, cnt, stats);
     if (stats) stats->scratch_bytes = call.scratch;
     return HZ_OK;

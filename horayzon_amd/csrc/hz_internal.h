@@ -375,6 +375,24 @@ struct ViewshedArgs {
 int viewshed_launch(const Scene *sc, const ShadowArgs &a, const ViewshedArgs &v, hipStream_t st);
 int viewshed_masked_launch(const uint8_t *mask, size_t n, int32_t *seen_count, hipStream_t st);
 
+// hz_sight.hip (hz_terrain_sight_height; device pointers; DESIGN.md section 4, clause 19): one launch of k_sight_refill over
+// the a.num_sun observers a.suns of a chunk.  Of `a` the inputs, suns, num_sun, out_f32 (the heights f32[num_sun][cells], or
+// null), count_work and counters are read.  lowest f32[cells] (null: not wanted) takes the minimum of the finite results over
+// the observers: the caller fills it with +inf before the first launch (sight_lowest_init_launch) and sets its masked cells
+// to NaN after the last (sight_masked_launch).  cells_reached i64[num_sun] (null: not wanted) += the cells with a finite
+// result per observer: the caller zeroes it.  heights: the checked table (hz_terrain_sight_height), device f32[num_heights].
+struct SightArgs {
+    const float *heights;
+    int num_heights;
+    float max_dist;
+    int has_max;                         // 0: no distance limit (max_dist is not read)
+    float *lowest;
+    int64_t *cells_reached;
+};
+int sight_launch(const Scene *sc, const ShadowArgs &a, const SightArgs &v, hipStream_t st);
+int sight_lowest_init_launch(size_t n, float *lowest, hipStream_t st);
+int sight_masked_launch(const uint8_t *mask, size_t n, float *lowest, hipStream_t st);
+
 // hz_subgrid.hip (hz_terrain_sw_dir_cor_coarse; device pointers): n u32[dim_0 / p0][dim_1 / p1] = unmasked cells per coarse
 // cell; one chunk of k positions of accumulate's scratch (codes and / or vals, [k][cells]) reduced to block means
 // f_cor / lit f32[k][gy][gx] (null: not wanted; f_cor needs vals, lit needs codes), coarse cells without a cell = fill

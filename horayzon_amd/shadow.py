@@ -374,6 +374,94 @@ class Terrain:
             int(bool(facing)), ptr(visible), ptr(seen_count), ptr(cells_seen), C.byref(st)))
         self.last_stats = st.as_dict()
 
+    # --- additive: the lowest target height in sight, per observer and cell --------------------------------------------
+    def sight_height(self, observers, heights, *, height=None, lowest=None, cells_reached=None, max_dist=None):
+        """How high above each cell a target must be to have a free line of sight to each point of observers f32[S][3]
+        (as in ``viewshed``), out of the table heights f32[n] [m] (1 <= n <= 65535, finite, strictly increasing,
+        heights[0] >= 0.005; a NumPy array, e.g. from ``sight_heights``): the smallest entry whose point above the surface
+        along ``vec_norm`` is in sight, found by asking for the top of the table, then its bottom, then bisecting
+        (clause 19) -- at most 2 + ceil(log2(n - 1)) rays per observer and cell instead of one
+        ``viewshed`` call per height.  +inf where not even the top of the table is in sight or the cell is farther than
+        ``max_dist`` [m] (None or > 0; judged at heights[0]); NaN where masked.  No facing test (an elevated target is
+        not a surface); refraction is never applied.  Where visibility is not monotone in the height the bisection
+        returns one visible entry above a blocked one, not necessarily the first.  Outputs, any subset, at least one:
+        ``height`` f32[S][y][x] the results, ``lowest`` f32[y][x] their minimum over the observers, ``cells_reached``
+        i64[S] the cells with a finite result per observer; NumPy or torch tensors on the Terrain's GPU.
+        ``last_stats["num_rays"]`` is the number of rays traced; ``last_stats["scratch_bytes"]`` does not grow with S."""
+        outs = (("height", height, 3, np.float32), ("lowest", lowest, 2, np.float32),
+                ("cells_reached", cells_reached, 1, np.int64))
+        self._array_arg(observers, 2, "observers")
+        if not isinstance(heights, np.ndarray):
+            raise TypeError("Argument 'heights' has incorrect type (expected numpy.ndarray, got %s)" % type(heights).__name__)
+        _typed(heights, np.float32, 1, "heights")
+        for name, buf, ndim, dtype in outs:
+            if buf is not None:
+                self._array_arg(buf, ndim, name, dtype)
+        if max_dist is not None and (not isinstance(max_dist, (int, float, np.integer, np.floating)) or
+                                     isinstance(max_dist, (bool, np.bool_))):
+            raise TypeError("Argument 'max_dist' has incorrect type (expected a number or None, got %s)" % type(max_dist).__name__)
+        given = [buf for _, buf, _, _ in outs if buf is not None]
+
+        def finite():
+            if _is_tensor(observers):
+                import torch
+                return bool(torch.isfinite(observers).all().item())
+            return bool(np.isfinite(observers).all())
+        V.run((
+            (ValueError, "at least one of 'height', 'lowest' and 'cells_reached' must be given", lambda: not given),
+            (ValueError, "array 'observers' has incorrect shape", lambda: observers.shape[1] != 3 or observers.shape[0] < 1),
+            (ValueError, "array 'heights' must have 1 to 65535 entries", lambda: not 1 <= heights.shape[0] <= 65535),
+            (ValueError, "array 'height' has incorrect shape",
+             lambda: height is not None and height.shape[0] != observers.shape[0]),
+            (ValueError, "array 'cells_reached' has incorrect shape",
+             lambda: cells_reached is not None and cells_reached.shape[0] != observers.shape[0]),
+            (ValueError, "not all input arrays are C-contiguous",
+             lambda: not all(_contiguous(a) for a in [observers, heights] + given)),
+            (ValueError, "'height', 'lowest' and 'cells_reached' must be different arrays",
+             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            (ValueError, "array 'heights' has non-finite entries", lambda: not np.isfinite(heights).all()),
+            (ValueError, "'heights' must start at 0.005 m or above", lambda: not heights[0] >= np.float32(0.005)),
+            (ValueError, "'heights' must be strictly increasing", lambda: not (heights[1:] > heights[:-1]).all()),
+            (ValueError, "'max_dist' must be None or greater than 0", lambda: max_dist is not None and not np.float32(max_dist) > 0),
+            (ValueError, "array 'observers' has non-finite entries", lambda: not finite()),
+        ))
+        for name, buf in (("height", height), ("lowest", lowest)):
+            if buf is not None:
+                self._check_out(buf, name)
+        if self._shape is None:
+            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
+        st = hz_stats()
+        _lib.check(_lib.lib().hz_terrain_sight_height(
+            self._h, ptr(observers), observers.shape[0], ptr(heights), heights.shape[0],
+            0.0 if max_dist is None else float(max_dist), ptr(height), ptr(lowest), ptr(cells_reached), C.byref(st)))
+        self.last_stats = st.as_dict()
+
+
+def sight_heights(height_max, height_acc=0.25, height_min=0.05):
+    """A height table for ``Terrain.sight_height``: float32 of height_min + k * height_acc, k = 0 ... K, formed in float64, with
+    K = ceil((height_max - height_min) / height_acc): the last entry is the first at or above height_max (it exceeds it by less
+    than one step).  ValueError if the table would have more than 65535 entries, if it would start below 0.005 m, or if
+    rounding to float32 makes two neighbours equal (a step too fine for the heights)."""
+    for name, v in (("height_max", height_max), ("height_acc", height_acc), ("height_min", height_min)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, (bool, np.bool_)):
+            raise TypeError("Argument '%s' has incorrect type (expected a number, got %s)" % (name, type(v).__name__))
+    lo, hi, acc = np.float64(height_min), np.float64(height_max), np.float64(height_acc)
+    if not (np.isfinite(lo) and np.isfinite(hi) and np.isfinite(acc)):
+        raise ValueError("'height_max', 'height_acc' and 'height_min' must be finite")
+    if not acc > 0.0:
+        raise ValueError("'height_acc' must be greater than 0")
+    if not np.float32(lo) >= np.float32(0.005):
+        raise ValueError("'height_min' must be at least 0.005 m")
+    if not hi >= lo:
+        raise ValueError("'height_max' must not be below 'height_min'")
+    steps = np.ceil((hi - lo) / acc)
+    if steps + 1 > 65535:
+        raise ValueError("the table would have %d entries (at most 65535)" % (int(steps) + 1))
+    table = (lo + np.arange(int(steps) + 1, dtype=np.float64) * acc).astype(np.float32)
+    if not (table[1:] > table[:-1]).all():
+        raise ValueError("'height_acc' is too small for float32: neighbouring entries are equal")
+    return table
+
 
 def _is_tensor(a):
     return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")

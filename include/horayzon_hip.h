@@ -626,6 +626,22 @@ int hz_terrain_sw_dir_cor_coarse(hz_terrain *terrain, const float *sun_positions
 /* and the batch calls share: it is kept with the handle, 12 bytes per observer of one launch, at most 32768 * 12 bytes         */
 int hz_terrain_viewshed(hz_terrain *terrain, const float *observers, int num_obs, float target_elev, float max_dist,
                         int facing, uint8_t *visible, int32_t *seen_count, int64_t *cells_seen, hz_stats *stats);
+/* additive: the lowest target height in sight per observer and cell (DESIGN.md section 4 clause 19).  observers as in          */
+/* hz_terrain_viewshed; heights f32[num_heights] is the caller's table H: 1 <= num_heights <= 65535, finite, strictly           */
+/* increasing, H[0] >= 0.005 [m] (checked here; HZ_ERR_ARG otherwise); the kernel indexes it and does no arithmetic on it.      */
+/* visible(k): T = v + norm * H[k], d = P - T, mag and u as in hz_terrain_viewshed; !(mag > 0) is visible without a ray; else   */
+/* one any-hit ray (T, u, tfar = mag), no hit = visible.  No facing test; never refracted.  Per observer and cell, in order:    */
+/*   mask[c] != 1 -> NaN;  a limit is given and mag(H[0]) > max_dist -> +inf (no ray);  !visible(n - 1) -> +inf;                 */
+/*   n == 1 or visible(0) -> H[0];  else lo = 0, hi = n - 1, while hi - lo > 1: mid = (lo + hi) >> 1,                            */
+/*   visible(mid) ? hi = mid : lo = mid;  the result is H[hi].                                                                   */
+/* height f32[num_obs][y][x] takes the results, lowest f32[y][x] their minimum over the observers (+inf where no observer is   */
+/* reached, NaN where masked), cells_reached i64[num_obs] the cells with a finite result per observer; NULL = not wanted (at   */
+/* least one; they must differ).  Every pointer may be host or device memory (a device table is read back for its checks).     */
+/* max_dist [m]: <= 0, NaN or infinite = no limit.  stats->num_rays = rays traced.  hz_stats.scratch_bytes = device memory the  */
+/* call allocates besides the caller's buffers: a host table (4 bytes per entry) and the staging of a host lowest; it does not */
+/* grow with num_obs.  Not counted: the staging of a host height / cells_reached and the handle's buffer for host observers.   */
+int hz_terrain_sight_height(hz_terrain *terrain, const float *observers, int num_obs, const float *heights, int num_heights,
+                            float max_dist, float *height, float *lowest, int64_t *cells_reached, hz_stats *stats);
 /* additive: 1 = later shadow / sw_dir_cor calls run the counting instantiation and also fill   */
 /* hz_stats.nodes_visited / tris_tested / wave_*_iters (slower; for the roofline's B_trav)      */
 int hz_terrain_count_work(hz_terrain *terrain, int on);
