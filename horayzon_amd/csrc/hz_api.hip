@@ -514,6 +514,11 @@ int hz_debug_set(const char *key, int value) {
             return hz::set_error(HZ_ERR_ARG, "hz_debug_set: horidist_block_w is 8, 16, 32 or 64");
         hz::g_horidist_block_w.store(value < 0 ? 8 : value, std::memory_order_relaxed);
     }
+    else if (!strcmp(key, "panorama_traversal")) {    // (< 0: the default; results never depend on it)
+        if (value > 1) return hz::set_error(HZ_ERR_ARG, "hz_debug_set: panorama_traversal is 0 or 1");
+        hz::g_panorama_traversal.store(value, std::memory_order_relaxed);
+    }
+    else if (!strcmp(key, "panorama_budget")) hz::g_panorama_budget.store(value < 0 ? 0 : value, std::memory_order_relaxed);
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
 }

@@ -2,13 +2,14 @@
 // Terrain (hz_terrain_*: rays against the scene, restating CppTerrain, shadow_comp.cpp:304-605) and HorizonTerrain
 // (hz_horizon_terrain_*: look-ups in a stored horizon).
 //
-// Eight calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
-// hz_terrain_viewshed, hz_terrain_sight_height, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
+// Nine calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
+// hz_terrain_viewshed, hz_terrain_sight_height, hz_terrain_panorama, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
 // allocations, one chunk loop with the launches, finish; what they share -- device, lock, stream, timers, the scratch tally,
 // staged inputs, staged outputs -- is SunCall and ChunkFeed below.
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
 #include "hz_horisun_coarse_plan.h"
+#include "hz_panorama_plan.h"
 #include <cmath>
 #include <vector>
 #include <mutex>
@@ -671,6 +672,81 @@ int hz_terrain_sight_height(hz_terrain *terrain, const float *observers, int num
     if ((rc = call.finish(stats, d_height, d_lowest, d_cells))) return rc;
     terrain_stats(t, cnt, stats);
     if (stats) stats->scratch_bytes = call.scratch;
+    return HZ_OK;
+}
+
+// Terrain.panorama (hz_panorama.hip: k_panorama; DESIGN.md section 4 clause 20).  Observers go in chunks (hz_panorama_plan.h):
+// a `dist` / `point` given as host memory is staged on the device one chunk at a time and copied out inside the loop, so the
+// staging -- what hz_stats.scratch_bytes reports, with the four tables if they came from the host and the chunk's observers
+// and frames if those did -- is held to the budget and does not grow with num_obs.  Device outputs are written in place.  A
+// host `hits` is staged whole (8 bytes per observer, not counted, as cells_seen of hz_terrain_viewshed).
+int hz_terrain_panorama(hz_terrain *terrain, const float *observers, int num_obs, const float *azim_sin, const float *azim_cos,
+                        int azim_num, const float *elev_sin, const float *elev_cos, int elev_num, const float *vec_north,
+                        const float *vec_norm, float max_dist, float *dist, float *point, int64_t *hits, hz_stats *stats) {
+    Terrain *t = reinterpret_cast<Terrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "Terrain is not initialised");
+    if (!observers || num_obs < 1) return set_error(HZ_ERR_ARG, "array 'observers' has incorrect shape");
+    if (!azim_sin || !azim_cos || azim_num < 1) return set_error(HZ_ERR_ARG, "the azimuth tables must have at least one entry");
+    if (!elev_sin || !elev_cos || elev_num < 1) return set_error(HZ_ERR_ARG, "the elevation tables must have at least one entry");
+    if ((unsigned long long)azim_num * (unsigned long long)elev_num > HZ_PANORAMA_MAX_PIXELS)
+        return set_error(HZ_ERR_ARG, "an image of %d x %d pixels exceeds 2^30", elev_num, azim_num);
+    if (!std::isfinite(max_dist) || !(max_dist > 0.0f)) return set_error(HZ_ERR_ARG, "'max_dist' must be finite and greater than 0");
+    if (!dist && !point && !hits) return set_error(HZ_ERR_ARG, "no output buffer (dist, point and hits are NULL)");
+    if ((vec_north == nullptr) != (vec_norm == nullptr)) return set_error(HZ_ERR_ARG, "'vec_north' and 'vec_norm' must be given together");
+    const void *outs[3] = {dist, point, hits};
+    int rc;
+    if ((rc = check_distinct_outputs(outs, 3))) return rc;
+    const bool stage_dist = dist && !is_device_ptr(dist), stage_point = point && !is_device_ptr(point);
+    const int knob = g_panorama_budget.load(std::memory_order_relaxed);       // (hz_debug_set("panorama_budget", bytes): tests)
+    PanoramaPlan plan;
+    if (!panorama_plan(num_obs, azim_num, elev_num, stage_dist, stage_point, knob > 0 ? (unsigned long long)knob : HZ_PANORAMA_BUDGET, &plan))
+        return set_error(HZ_ERR_ARG, "panorama: no plan for %d observers of %d x %d pixels", num_obs, elev_num, azim_num);
+    SunCall call;
+    if ((rc = call.start(t->device, t->scene->run_mu, t->stream))) return rc;
+    const int k = plan.chunk;
+    const size_t pixels = (size_t)plan.pixels;
+    ChunkFeed<float> obs(observers, 3), north(vec_north, 3), norm(vec_norm, 3);
+    if ((rc = vec_north ? call.stage(k, obs, north, norm) : call.stage(k, obs))) return rc;
+    PanoramaArgs a;
+    DevIn<float> d_as, d_ac, d_es, d_ec;
+    if ((rc = d_as.bind(azim_sin, (size_t)azim_num, call.st)) || (rc = d_ac.bind(azim_cos, (size_t)azim_num, call.st)) ||
+        (rc = d_es.bind(elev_sin, (size_t)elev_num, call.st)) || (rc = d_ec.bind(elev_cos, (size_t)elev_num, call.st)))
+        return rc;
+    call.scratch += ((d_as.owned ? 1 : 0) + (d_ac.owned ? 1 : 0)) * (size_t)azim_num * sizeof(float) +
+                    ((d_es.owned ? 1 : 0) + (d_ec.owned ? 1 : 0)) * (size_t)elev_num * sizeof(float);
+    a.azim_sin = d_as.dev; a.azim_cos = d_ac.dev; a.elev_sin = d_es.dev; a.elev_cos = d_ec.dev;
+    a.azim_num = azim_num; a.elev_num = elev_num; a.max_dist = max_dist;
+    // a staged output holds one chunk; an output in device memory is the caller's whole array
+    DevOut<float> d_dist, d_point; DevOut<int64_t> d_hits;
+    if ((rc = call.bind(d_dist, dist, stage_dist ? (size_t)k * pixels : (size_t)num_obs * pixels, true)) ||
+        (rc = call.bind(d_point, point, 3 * (stage_point ? (size_t)k * pixels : (size_t)num_obs * pixels), true)) ||
+        (rc = call.bind(d_hits, hits, (size_t)num_obs, false)))
+        return rc;
+    if (d_hits.dev) HZ_HIP(hipMemsetAsync(d_hits.dev, 0, (size_t)num_obs * sizeof(int64_t), call.st));
+    if ((rc = terrain_begin(t, call))) return rc;
+    for (int s0 = 0; s0 < num_obs; s0 += k) {
+        a.num_obs = std::min(k, num_obs - s0);
+        if ((rc = obs.at(s0, a.num_obs, call.st, &a.observers)) || (rc = north.at(s0, a.num_obs, call.st, &a.vec_north)) ||
+            (rc = norm.at(s0, a.num_obs, call.st, &a.vec_norm)))
+            return rc;
+        a.dist = d_dist.dev ? d_dist.dev + (stage_dist ? 0 : pixels * (size_t)s0) : nullptr;
+        a.point = d_point.dev ? d_point.dev + (stage_point ? 0 : 3 * pixels * (size_t)s0) : nullptr;
+        a.hits = d_hits.dev ? d_hits.dev + s0 : nullptr;
+        if ((rc = panorama_launch(t->scene, a, call.st))) return rc;
+        // the chunk's staged images go out before the next chunk is traced into the same memory (stream order)
+        if (stage_dist)
+            HZ_HIP(hipMemcpyAsync(dist + pixels * (size_t)s0, d_dist.dev, (size_t)a.num_obs * pixels * sizeof(float), hipMemcpyDeviceToHost, call.st));
+        if (stage_point)
+            HZ_HIP(hipMemcpyAsync(point + 3 * pixels * (size_t)s0, d_point.dev, 3 * (size_t)a.num_obs * pixels * sizeof(float), hipMemcpyDeviceToHost, call.st));
+    }
+    unsigned long long cnt[HZ_SHADOW_CNT_N];
+    if ((rc = terrain_end(t, call, cnt))) return rc;
+    if ((rc = call.finish(stats, d_hits))) return rc;
+    terrain_stats(t, cnt, stats);
+    if (stats) {
+        stats->num_rays += (unsigned long long)num_obs * plan.pixels;      // every pixel is one ray
+        stats->scratch_bytes = call.scratch;
+    }
     return HZ_OK;
 }
 

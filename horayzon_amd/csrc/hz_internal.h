@@ -468,6 +468,24 @@ int horidist_launch(const Scene *sc, const HoridistArgs &a, hipStream_t st);
 extern std::atomic<int> g_horidist_traversal;   // "horidist_traversal" (hz_debug_set): 0 hz_closest's slot order, 1 (default, also < 0) the children of a node front to back
 extern std::atomic<int> g_horidist_block_w;  // "horidist_block_w" (hz_debug_set): cells per row of a wave's block in the planes launches (default 8)
 
+// hz_panorama.hip (hz_terrain_panorama; device pointers; DESIGN.md section 4, clause 20): one launch of k_panorama over the
+// num_obs observers of a chunk, one wave per 8 x 8 tile of an observer's elev_num x azim_num image (tiles * num_obs < 2^31:
+// hz_panorama_plan.h).  vec_north / vec_norm f32[num_obs][3], or both null = the planar frame.  The outputs start at the
+// chunk's first observer: dist f32[num_obs][elev_num][azim_num], point f32[num_obs][elev_num][azim_num][3], hits
+// i64[num_obs] += the pixels with a hit (the caller zeroes it); null: not wanted.
+struct PanoramaArgs {
+    const float *observers, *vec_north, *vec_norm;
+    int num_obs;
+    const float *azim_sin, *azim_cos, *elev_sin, *elev_cos;      // device tables
+    int azim_num, elev_num;
+    float max_dist;
+    float *dist, *point;
+    int64_t *hits;
+};
+int panorama_launch(const Scene *sc, const PanoramaArgs &a, hipStream_t st);
+extern std::atomic<int> g_panorama_traversal;   // "panorama_traversal" (hz_debug_set): 0 hz_closest's slot order, 1 (default, also < 0) the children of a node front to back
+extern std::atomic<int> g_panorama_budget;      // "panorama_budget" (hz_debug_set): > 0 bytes of staged output per chunk of hz_terrain_panorama (default 0: HZ_PANORAMA_BUDGET)
+
 // hz_horisun_coarse.hip (hz_horizon_terrain_sw_dir_cor_coarse; device pointers): the plan of the fused kernel for chunks of
 // up to `chunk` positions (hz_horisun_coarse_plan.h; plan->fallback = 1: the shape, the "horisun_coarse_route" knob or the layout's default asks
 // for the two-pass route), and one launch of k_horisun_coarse over the a.num_sun <= chunk positions of a chunk: block means

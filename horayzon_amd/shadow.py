@@ -374,6 +374,87 @@ class Terrain:
             int(bool(facing)), ptr(visible), ptr(seen_count), ptr(cells_seen), C.byref(st)))
         self.last_stats = st.as_dict()
 
+    # --- additive: depth images of the terrain from observer points -----------------------------------------------------
+    def panorama(self, observers, azim, elev, max_dist, *, dist=None, point=None, hits=None,
+                 vec_north=None, vec_norm=None):
+        """Looking out from each point of observers f32[S][3] (as in ``viewshed``: the scene's frame; NumPy or a torch
+        tensor on the Terrain's GPU; finite) in the directions azim f32[A] x elev f32[E] (NumPy, radians, finite, A >= 1,
+        E >= 1, E * A <= 2**30; azimuth clockwise from north, elevation in [-pi/2, pi/2] as float32; any order or spacing):
+        how far away is the terrain, and where does the ray land?  One closest-hit ray of length ``max_dist`` [m] (a
+        number, finite and > 0 as float32) per observer and pixel, against the whole scene (clause
+        20); ``mask``, ``vec_tilt`` and the inner-domain offsets play no part and refraction is never applied.
+        ``vec_north`` / ``vec_norm`` f32[S][3] (NumPy, unit vectors, both or neither) give each observer's local frame, e.g.
+        on a curved DEM; with neither, north = (0, 1, 0) and norm = (0, 0, 1).  Outputs, any subset, at least one, every
+        element written: ``dist`` f32[S][E][A] the distance to the closest triangle, NaN where nothing is hit within
+        ``max_dist``; ``point`` f32[S][E][A][3] the hit point observer + direction * distance (NaN x 3 where nothing is
+        hit); ``hits`` i64[S] the pixels with a hit; NumPy or torch tensors on the Terrain's GPU.  An observer on the
+        surface hits it at distance 0.0.  ``last_stats["num_rays"]`` is S * E * A.  Observers go in chunks: NumPy images
+        are staged on the device one chunk at a time (at most 256 MiB, or one observer's images), so
+        ``last_stats["scratch_bytes"]`` does not grow with S.  The finiteness check of observers given as a tensor reads a
+        reduction back from the GPU: one device synchronisation per call before the launches."""
+        outs = (("dist", dist, 3, np.float32), ("point", point, 4, np.float32), ("hits", hits, 1, np.int64))
+        self._array_arg(observers, 2, "observers")
+        for name, tab in (("azim", azim), ("elev", elev)):
+            _typed(tab, np.float32, 1, name)
+        if not isinstance(max_dist, (int, float, np.integer, np.floating)) or isinstance(max_dist, (bool, np.bool_)):
+            raise TypeError("Argument 'max_dist' has incorrect type (expected a number, got %s)" % type(max_dist).__name__)
+        for name, buf, ndim, dtype in outs:
+            if buf is not None:
+                self._array_arg(buf, ndim, name, dtype)
+        frames = [(name, v) for name, v in (("vec_north", vec_north), ("vec_norm", vec_norm)) if v is not None]
+        for name, v in frames:
+            _typed(v, np.float32, 2, name)
+        given = [buf for _, buf, _, _ in outs if buf is not None]
+
+        def finite():
+            if _is_tensor(observers):
+                import torch
+                return bool(torch.isfinite(observers).all().item())
+            return bool(np.isfinite(observers).all())
+
+        def image_shape():
+            return (observers.shape[0], elev.shape[0], azim.shape[0])
+        half_pi = np.float32(np.pi / 2)
+        with np.errstate(over="ignore"):
+            tfar = np.float32(max_dist)                      # the ray length the kernel sees
+        V.run((
+            (ValueError, "at least one of 'dist', 'point' and 'hits' must be given", lambda: not given),
+            (ValueError, "array 'observers' has incorrect shape", lambda: observers.shape[1] != 3 or observers.shape[0] < 1),
+            (ValueError, "array 'azim' must have at least one entry", lambda: azim.shape[0] < 1),
+            (ValueError, "array 'elev' must have at least one entry", lambda: elev.shape[0] < 1),
+            (ValueError, "an image of 'elev' x 'azim' must not have more than 2**30 pixels",
+             lambda: elev.shape[0] * azim.shape[0] > 2 ** 30),
+            (ValueError, "array 'dist' has incorrect shape", lambda: dist is not None and tuple(dist.shape) != image_shape()),
+            (ValueError, "array 'point' has incorrect shape",
+             lambda: point is not None and tuple(point.shape) != image_shape() + (3,)),
+            (ValueError, "array 'hits' has incorrect shape", lambda: hits is not None and hits.shape[0] != observers.shape[0]),
+            (ValueError, "'vec_north' and 'vec_norm' must be given together", lambda: len(frames) == 1),
+            (ValueError, "Inconsistent/incorrect shape of 'vec_north' and/or 'vec_norm'",
+             lambda: any(tuple(v.shape) != (observers.shape[0], 3) for _, v in frames)),
+            (ValueError, "not all input arrays are C-contiguous",
+             lambda: not all(_contiguous(a) for a in [observers, azim, elev] + [v for _, v in frames] + given)),
+            (ValueError, "'dist', 'point' and 'hits' must be different arrays",
+             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            (ValueError, "'max_dist' must be finite and greater than 0", lambda: not (np.isfinite(tfar) and tfar > 0)),
+            (ValueError, "array 'azim' has non-finite entries", lambda: not np.isfinite(azim).all()),
+            (ValueError, "array 'elev' has non-finite entries", lambda: not np.isfinite(elev).all()),
+            (ValueError, "'elev' must lie in [-pi/2, pi/2]", lambda: bool((elev < -half_pi).any() or (elev > half_pi).any())),
+            (ValueError, "Vectors in 'vec_north' and/or 'vec_norm' are not normalised",
+             lambda: not all(V.unit_vectors(v[None]) for _, v in frames)),
+            (ValueError, "array 'observers' has non-finite entries", lambda: not finite()),
+        ))
+        if self._shape is None:
+            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
+        # the four tables of the clause: float64 sin / cos, rounded to float32 once
+        azim_sin, azim_cos = np.sin(azim.astype(np.float64)).astype(np.float32), np.cos(azim.astype(np.float64)).astype(np.float32)
+        elev_sin, elev_cos = np.sin(elev.astype(np.float64)).astype(np.float32), np.cos(elev.astype(np.float64)).astype(np.float32)
+        st = hz_stats()
+        _lib.check(_lib.lib().hz_terrain_panorama(
+            self._h, ptr(observers), observers.shape[0], ptr(azim_sin), ptr(azim_cos), azim.shape[0],
+            ptr(elev_sin), ptr(elev_cos), elev.shape[0], ptr(vec_north), ptr(vec_norm), float(tfar),
+            ptr(dist), ptr(point), ptr(hits), C.byref(st)))
+        self.last_stats = st.as_dict()
+
     # --- additive: the lowest target height in sight, per observer and cell --------------------------------------------
     def sight_height(self, observers, heights, *, height=None, lowest=None, cells_reached=None, max_dist=None):
         """How high above each cell a target must be to have a free line of sight to each point of observers f32[S][3]

@@ -499,7 +499,9 @@ int hz_debug_inst_rate(int device, int op, double *cycles_per_inst);
 /* "regroup_round" = 0 ... 63: the rounding addend of that scaled threshold, (regroup * lanes + round) >> 6 (< 0: the default),  */
 /* "horidist_traversal" = 0: the distance kernel of hz_horizon_distance runs hz_closest's slot order (1 or < 0: the default,   */
 /* the children of a node front to back), "horidist_block_w" = 16, 32, 64: cells per row of a wave's block in                  */
-/* hz_horizon_distance (8 or < 0: the default, 8 x 8 cells)                                                                     */
+/* hz_horizon_distance (8 or < 0: the default, 8 x 8 cells),                                                                    */
+/* "panorama_traversal" = 0: the kernel of hz_terrain_panorama runs hz_closest's slot order (1 or < 0: the default, the children */
+/* of a node front to back), "panorama_budget" = n > 0: bytes of staged output per chunk of hz_terrain_panorama (<= 0: 256 MiB)  */
 int hz_debug_set(const char *key, int value);
 
 /* ------------------------------------------------------------------------- */
@@ -642,6 +644,29 @@ int hz_terrain_viewshed(hz_terrain *terrain, const float *observers, int num_obs
 /* grow with num_obs.  Not counted: the staging of a host height / cells_reached and the handle's buffer for host observers.   */
 int hz_terrain_sight_height(hz_terrain *terrain, const float *observers, int num_obs, const float *heights, int num_heights,
                             float max_dist, float *height, float *lowest, int64_t *cells_reached, hz_stats *stats);
+/* additive: depth images of the scene from observer points (DESIGN.md section 4 clause 20).  observers f32[num_obs][3] as in   */
+/* hz_terrain_viewshed.  An image has elev_num x azim_num pixels; the caller passes the four float32 tables                      */
+/* azim_sin / azim_cos f32[azim_num] and elev_sin / elev_cos f32[elev_num] (float64 sin / cos of the angles, rounded once;      */
+/* azimuth clockwise from north): the kernel does no trigonometry.  vec_north, vec_norm f32[num_obs][3]: the unit vectors of    */
+/* each observer's frame, both or neither (both NULL: north = (0, 1, 0), norm = (0, 0, 1)).  All float32, every product and sum */
+/* rounded on its own.  Per observer s and pixel (e, a):                                                                         */
+/*   east = north x norm;  rx = elev_cos[e] * azim_sin[a], ry = elev_cos[e] * azim_cos[a], rz = elev_sin[e];                     */
+/*   dir = (east * rx + north * ry) + norm * rz;  one closest-hit ray (observer, dir, tfar = max_dist);                          */
+/*   dist[s][e][a] = the minimum t over all accepted triangles, NaN if there is none;  point[s][e][a][c] = obs[c] + dir[c] * t   */
+/*   (NaN x 3 if there is none);  hits[s] = the pixels of observer s with a hit.  A minimum that is zero is written as +0.0     */
+/*   (an observer on the surface is accepted with T = +0 and T = -0 by the triangles around it), and point uses that value.     */
+/* dist f32[num_obs][elev_num][azim_num], point f32[num_obs][elev_num][azim_num][3], hits i64[num_obs]; NULL = not wanted (at    */
+/* least one; they must differ); every element is written.  Every pointer may be host or device memory.  Never refracted; mask, */
+/* vec_tilt and the inner-domain offsets play no part.  HZ_ERR_ARG for counts < 1, elev_num * azim_num > 2^30, max_dist not      */
+/* finite or <= 0, no output, or exactly one of the two frame arrays.  stats->num_rays = num_obs * elev_num * azim_num.          */
+/* Observers go in chunks: a host dist / point is staged on the device one chunk at a time, at most 256 MiB                      */
+/* ("panorama_budget" of hz_debug_set) or one observer's images.  hz_stats.scratch_bytes = that staging, host tables and the     */
+/* chunk's host observers and frames; it does not grow with num_obs.  Not counted: the staging of a host hits (8 bytes each).    */
+int hz_terrain_panorama(hz_terrain *terrain, const float *observers, int num_obs,
+                        const float *azim_sin, const float *azim_cos, int azim_num,
+                        const float *elev_sin, const float *elev_cos, int elev_num,
+                        const float *vec_north, const float *vec_norm,   /* both NULL: planar frame */
+                        float max_dist, float *dist, float *point, int64_t *hits, hz_stats *stats);
 /* additive: 1 = later shadow / sw_dir_cor calls run the counting instantiation and also fill   */
 /* hz_stats.nodes_visited / tris_tested / wave_*_iters (slower; for the roofline's B_trav)      */
 int hz_terrain_count_work(hz_terrain *terrain, int on);

@@ -3,7 +3,9 @@
     python scripts/kernel_asm.py sha [tree]           -> one sha256 over the normalised gfx950 assembly of the kernels the counter files
                                                           describe (PROFILED: production launch of k_horizon, its follow-up launch,
                                                           k_shadow_refill) of `tree` (default: this repository)
-    python scripts/kernel_asm.py diff treeA treeB      -> per source file: identical, or the kernels whose bodies differ (exit status 1)
+    python scripts/kernel_asm.py diff treeA treeB [src.hip ... | --all]
+                                                       -> per source file: identical, or the kernels whose bodies differ (exit status 1);
+                                                          the files named, --all: every source of treeB's Makefile, none: the three above
     python scripts/kernel_asm.py stamp                 -> writes profiles/kernel_asm.sha (the stamp profiles/valu_model.json, traffic.json and
                                                           valu_class_mix.json carry: they describe THIS machine code, not the source text)
 
@@ -63,11 +65,22 @@ def kernels(lines):
     return out
 
 
-def assemblies(tree):
-    """{source: normalised listing}, the three compilations side by side."""
+def assemblies(tree, sources=SOURCES):
+    """{source: normalised listing}, the compilations side by side (None: the tree has no such file)."""
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(len(SOURCES)) as ex:
-        return dict(zip(SOURCES, ex.map(lambda s_: normalise(assembly(tree, s_)), SOURCES)))
+
+    def one(src):
+        if not os.path.exists(os.path.join(tree, "horayzon_amd", "csrc", src)):
+            return None
+        return normalise(assembly(tree, src))
+    with ThreadPoolExecutor(min(len(sources), os.cpu_count() or 1)) as ex:
+        return dict(zip(sources, ex.map(one, sources)))
+
+
+def makefile_sources(tree):
+    """Every source the library of `tree` is built from (SRCS of its Makefile)."""
+    out = subprocess.run(["make", "-s", "-C", os.path.join(tree, "horayzon_amd", "csrc"), "print-srcs"], capture_output=True, text=True, check=True)
+    return tuple(out.stdout.split())
 
 
 # the kernels the counter files under profiles/ describe: production launch of k_horizon, its follow-up launch, the shadow kernel
@@ -92,10 +105,13 @@ def sha(tree=ROOT):
     return h.hexdigest()
 
 
-def diff(a, b):
+def diff(a, b, sources=SOURCES):
     rc = 0
-    asm_a, asm_b = assemblies(a), assemblies(b)
-    for src in SOURCES:
+    asm_a, asm_b = assemblies(a, sources), assemblies(b, sources)
+    for src in sources:
+        if asm_a[src] is None or asm_b[src] is None:
+            print("%-18s only in %s" % (src, a if asm_b[src] is None else b))
+            continue
         ka, kb = kernels(asm_a[src]), kernels(asm_b[src])
         bad = sorted(k for k in set(ka) | set(kb) if ka.get(k) != kb.get(k))
         if not bad:
@@ -114,7 +130,8 @@ if __name__ == "__main__":
     if cmd == "sha":
         print(sha(sys.argv[2] if len(sys.argv) > 2 else ROOT))
     elif cmd == "diff":
-        sys.exit(diff(sys.argv[2], sys.argv[3]))
+        named = tuple(sys.argv[4:])
+        sys.exit(diff(sys.argv[2], sys.argv[3], makefile_sources(sys.argv[3]) if named == ("--all",) else (named or SOURCES)))
     elif cmd == "stamp":
         v = sha()
         with open(os.path.join(ROOT, "profiles", "kernel_asm.sha"), "w") as f:
