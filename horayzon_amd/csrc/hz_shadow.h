@@ -1,6 +1,6 @@
-// hz_shadow.h -- what the refill kernels of hz_shadow.hip (k_shadow_refill, k_accum_refill) and hz_viewshed.hip
-// (k_viewshed_refill) share: the kernel parameters, the tuning constants of the refill loop, the launch configuration and
-// two small device functions.  Moved here word for word: the machine code of hz_shadow.hip's kernels does not change.
+// hz_shadow.h -- what the four refill kernels (k_shadow_refill, k_accum_refill: hz_shadow.hip; k_viewshed_refill:
+// hz_viewshed.hip; k_sight_refill: hz_sight.hip) share beside their loop (hz_refill_loop.inc): the kernel parameters, the
+// tuning constants of the loop, the launch configuration, the launch itself and two small device functions.
 #pragma once
 #include "hz_internal.h"
 
@@ -63,8 +63,21 @@ __device__ __forceinline__ void shadow_counters(const ShadowParams &p, unsigned 
 #define HZ_SHADOW_WG 7
 #endif
 
-// Launch configuration of the refill kernels (k_shadow_refill, k_accum_refill, k_viewshed_refill) for one launch of a.num_sun
-// positions: parameters, dynamic LDS, grid, and whether the fast stack is used.  Returns 0 when there is nothing to launch.
+// Launch configuration of the refill kernels for one launch of a.num_sun positions: parameters, dynamic LDS, grid, and
+// whether the fast stack is used.  Returns 0 when there is nothing to launch.
 int shadow_config(const Scene *sc, const ShadowArgs &a, ShadowParams &p, size_t &lds, dim3 &grid, bool &fast);
+
+// The four instantiations of a refill kernel `template <bool COUNT, bool FAST> __global__ void K(Params)` as [count][fast],
+// and the launch of the one a call asks for, with the configuration of shadow_config.
+#define HZ_REFILL_KERNELS(K) {{K<false, false>, K<false, true>}, {K<true, false>, K<true, true>}}
+template <class Params>
+int refill_launch(void (*const (&kernels)[2][2])(Params), const Params &params, int count_work, bool fast, dim3 grid, size_t lds,
+                  hipStream_t st) {
+    void (*const k)(Params) = kernels[count_work ? 1 : 0][fast ? 1 : 0];
+    HZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, st, params);        // (256: the kernels' HZ_TPB)
+    HZ_HIP(hipGetLastError());
+    return HZ_OK;
+}
 
 }  // namespace hz

@@ -138,86 +138,29 @@ __device__ __forceinline__ void shadow_result(const ShadowParams &p, size_t cell
 }
 
 
-// k_shadow_refill: a wave owns p.nb consecutive 8 x 8 blocks (the same quadrant of nb neighbouring 16 x 16
-// tiles) and hands their cells to its lanes as they become free.  The rays of one sun position are parallel, so with one
-// ray per lane traced to completion (the round-2 kernel k_shadow, removed in round 6) a wave lasted as long as its longest
-// ray while most lanes idled (45 % of the lanes active per VALU instruction, profiles/r02/pmc_shadow_summary.json); here a
-// lane whose ray is finished takes the next cell once fewer than `regroup` lanes are still traversing (the ray compaction of
-// the horizon kernel).  Cells are handed out in block order, so the rays in flight stay neighbours.
 #ifndef HZ_SHADOW_FAST_CAP_DEFAULT
 #define HZ_SHADOW_FAST_CAP_DEFAULT 19   // 21 KiB of LDS per workgroup: 7 resident; round 4: level stack 1.074 -> fast stack 0.964 ms per position at 5 workgroups (profiles/r04/ab_shadow_fast_stack.log)
 #endif
-// FAST: the fast stack discipline of hz_trace (every pending sibling its own entry, written for the fewest instructions;
-// `stack_cap` entries behind two padding rows).  A ray that runs out of entries is traced again, to completion, with the
-// one-entry-per-level discipline in the same LDS column of its lane (the launcher makes sure the tree's height fits).
-// COUNT: also count node visits / triangle tests / wave-level steps (Terrain count_work; the roofline's B_trav)
+// k_shadow_refill: the refill loop (hz_refill_loop.inc: the scheme, COUNT and FAST) with at most one ray per cell towards the
+// sun, tfar = infinity.
 template <bool COUNT, bool FAST>
 __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SHADOW_WG) void k_shadow_refill(ShadowParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int *stack = reinterpret_cast<int *>(smem + (FAST ? 2 * HZ_TPB * 4 : 0));
-    const int tid = threadIdx.x;
-    int ti = 0, tj = 0;
-    const bool has_tile = hz_tile_of_block(p.tm, blockIdx.x, &ti, &tj);      // tile map over super tiles (16 x 16 nb cells)
-    const int wave = tid >> 6, lane = tid & 63;
-    const int sun_idx = blockIdx.y;
-    const float p_sun_x = p.suns[3 * sun_idx], p_sun_y = p.suns[3 * sun_idx + 1], p_sun_z = p.suns[3 * sun_idx + 2];
-    uint8_t *const out_u8 = p.out_u8 ? p.out_u8 + (size_t)sun_idx * p.out_stride : nullptr;
-    float *const out_f32 = p.out_f32 ? p.out_f32 + (size_t)sun_idx * p.out_stride : nullptr;
-    unsigned rays = 0;
-    TravCounters tc; tc.nodes = 0; tc.tris = 0; tc.w_nodes = 0; tc.w_leaves = 0;
-    const int i_base = ti * 16 + (wave >> 1) * 8, j_base = tj * (16 * p.nb) + (wave & 1) * 8;
-    const int total = has_tile ? 64 * p.nb : 0;
-    int next = 0;                                   // cells handed out so far (wave uniform)
-    bool ray_active = false;
-    ShadowRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.dot_ts = r.dot_ns = 0.0f;
+#define HZ_REFILL_OUTPUTS uint8_t *const out_u8 = HZ_REFILL_OUT_AT(p.out_u8); float *const out_f32 = HZ_REFILL_OUT_AT(p.out_f32);
+#define HZ_REFILL_LANE \
+    bool ray_active = false; \
+    ShadowRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.dot_ts = r.dot_ns = 0.0f; \
     size_t cell = 0;
-    RayBox rb = hz_raybox(0, 0, 0, 0, 0, 1);
-    TravState ts; hz_trav_reset(ts);
-    bool overflow = false;
-    for (;;) {
-        if (next < total) {
-            const unsigned long long need = __ballot(!ray_active);
-            if (need != 0ull) {
-                const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
-                const int my = next + rank;
-                next += __popcll(need);
-                if (!ray_active && my < total) {
-                    const int i = i_base + ((my & 63) >> 3), j = j_base + (my >> 6) * 16 + (my & 7);
-                    if (i < p.dim_in_0 && j < p.dim_in_1 && shadow_setup(p, i, j, p_sun_x, p_sun_y, p_sun_z, out_u8, out_f32, r)) {
-                        cell = (size_t)i * p.dim_in_1 + j;
-                        // (box tests start at -tau: hz_common.h; tfar is infinite here)
-                        rb = hz_raybox((r.ox - p.sv.cx) - p.sv.tau * r.dx, (r.oy - p.sv.cy) - p.sv.tau * r.dy, (r.oz - p.sv.cz) - p.sv.tau * r.dz,
-                                       r.dx, r.dy, r.dz);
-                        hz_trav_reset(ts);
-                        overflow = false;
-                        ray_active = true;
-                        rays++;
-                    }
-                }
-            }
-        }
-        if (__ballot(ray_active) == 0ull) {
-            if (next >= total) break;
-            continue;
-        }
-        if (ray_active) {
-            // while cells are left the traversal returns when fewer than 40 lanes are busy (and one finished)
-            int res = hz_trace<HZ_TPB, COUNT, 2, false, !FAST>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                    __builtin_inff(), __builtin_inff(), rb, ts, (next < total) ? HZ_SHADOW_REGROUP : 0, HZ_SHADOW_LEAF_BIAS, tc, p.stack_cap, overflow);
-            if (FAST && res != 2 && overflow) {
-                bool unused = false;
-                hz_trav_reset(ts);
-                res = hz_trace<HZ_TPB, COUNT, 2, false, true>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                                    __builtin_inff(), __builtin_inff(), rb, ts, 0, HZ_SHADOW_LEAF_BIAS, tc, 0, unused);
-                if (COUNT && p.counters) atomicAdd(&p.counters[HZ_SHADOW_CNT_TWICE], 1ull);     // rays traced twice
-            }
-            if (res != 2) {
-                shadow_result(p, cell, res == 1, r, out_u8, out_f32);
-                ray_active = false;
-            }
-        }
-    }
-    shadow_counters<COUNT>(p, rays, tc, lane);
+#define HZ_REFILL_PASS
+#define HZ_REFILL_BUSY ray_active
+#define HZ_REFILL_TAKE(i, j) \
+    if (shadow_setup(p, i, j, pos_x, pos_y, pos_z, out_u8, out_f32, r)) { cell = (size_t)i * p.dim_in_1 + j; HZ_REFILL_START_RAY(r); ray_active = true; }
+#define HZ_REFILL_PREPARE
+#define HZ_REFILL_TFAR __builtin_inff()
+#define HZ_REFILL_TFAR_BOX __builtin_inff()
+#define HZ_REFILL_REGROUP ((next < total) ? HZ_SHADOW_REGROUP : 0)      // while cells are left
+#define HZ_REFILL_DECIDED(res) shadow_result(p, cell, res == 1, r, out_u8, out_f32); ray_active = false;
+#define HZ_REFILL_END
+#include "hz_refill_loop.inc"
 }
 
 std::atomic<int> g_shadow_fast_cap{HZ_SHADOW_FAST_CAP_DEFAULT};      // hz_debug_set (hz_internal.h)
@@ -270,18 +213,12 @@ int shadow_config(const Scene *sc, const ShadowArgs &a, ShadowParams &p, size_t 
     return 1;
 }
 
-#define HZ_LAUNCH_REFILL(K, P) do { \
-        HZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(K, grid, dim3(HZ_TPB), lds, st, P); } while (0)
-
 int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st) {
+    static void (*const kernels[2][2])(ShadowParams) = HZ_REFILL_KERNELS(k_shadow_refill);
     ShadowParams p;
     size_t lds = 0; dim3 grid; bool fast = false;
     if (!shadow_config(sc, a, p, lds, grid, fast)) return HZ_OK;
-    if (fast) { if (a.count_work) HZ_LAUNCH_REFILL((k_shadow_refill<true, true>), p); else HZ_LAUNCH_REFILL((k_shadow_refill<false, true>), p); }
-    else { if (a.count_work) HZ_LAUNCH_REFILL((k_shadow_refill<true, false>), p); else HZ_LAUNCH_REFILL((k_shadow_refill<false, false>), p); }
-    HZ_HIP(hipGetLastError());
-    return HZ_OK;
+    return refill_launch(kernels, p, a.count_work, fast, grid, lds, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -295,9 +232,8 @@ int shadow_launch(const Scene *sc, const ShadowArgs &a, hipStream_t st) {
 // float64 accumulators in ascending position order, and k_accum_final rounds them to float32 once and writes the fill
 // value to masked cells.
 //
-// k_accum_refill is k_shadow_refill's loop with another result step.  It is a kernel of its own, not a template parameter
-// of k_shadow_refill: k_shadow_refill<false, true> is one of the kernels whose device assembly stamps profiles/*.json
-// (scripts/kernel_asm.py), and its machine code must not move.
+// k_accum_refill is a __global__ of its own on the shared loop, k_shadow_refill's hooks with another result step (why the
+// loop is shared as text, not as a template parameter of k_shadow_refill: hz_refill_loop.inc).
 struct AccumParams {
     ShadowParams s;          // s.which = 0: shadow codes to s.out_u8 (+ correction of the lit cells to s.out_f32); 1: correction only
     int want_sw;             // s.which == 0: also write the correction factor
@@ -321,82 +257,32 @@ __device__ __forceinline__ void accum_result(const AccumParams &p, size_t cell, 
 template <bool COUNT, bool FAST>
 __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SHADOW_WG) void k_accum_refill(AccumParams ap) {
     const ShadowParams &p = ap.s;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int *stack = reinterpret_cast<int *>(smem + (FAST ? 2 * HZ_TPB * 4 : 0));
-    const int tid = threadIdx.x;
-    int ti = 0, tj = 0;
-    const bool has_tile = hz_tile_of_block(p.tm, blockIdx.x, &ti, &tj);
-    const int wave = tid >> 6, lane = tid & 63;
-    const int sun_idx = blockIdx.y;
-    const float p_sun_x = p.suns[3 * sun_idx], p_sun_y = p.suns[3 * sun_idx + 1], p_sun_z = p.suns[3 * sun_idx + 2];
-    uint8_t *const out_u8 = p.out_u8 ? p.out_u8 + (size_t)sun_idx * p.out_stride : nullptr;
-    float *const out_f32 = p.out_f32 ? p.out_f32 + (size_t)sun_idx * p.out_stride : nullptr;
-    unsigned rays = 0;
-    TravCounters tc; tc.nodes = 0; tc.tris = 0; tc.w_nodes = 0; tc.w_leaves = 0;
-    const int i_base = ti * 16 + (wave >> 1) * 8, j_base = tj * (16 * p.nb) + (wave & 1) * 8;
-    const int total = has_tile ? 64 * p.nb : 0;
-    int next = 0;
-    bool ray_active = false;
-    ShadowRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.dot_ts = r.dot_ns = 0.0f;
+#define HZ_REFILL_OUTPUTS uint8_t *const out_u8 = HZ_REFILL_OUT_AT(p.out_u8); float *const out_f32 = HZ_REFILL_OUT_AT(p.out_f32);
+#define HZ_REFILL_LANE \
+    bool ray_active = false; \
+    ShadowRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.dot_ts = r.dot_ns = 0.0f; \
     size_t cell = 0;
-    RayBox rb = hz_raybox(0, 0, 0, 0, 0, 1);
-    TravState ts; hz_trav_reset(ts);
-    bool overflow = false;
-    for (;;) {
-        if (next < total) {
-            const unsigned long long need = __ballot(!ray_active);
-            if (need != 0ull) {
-                const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
-                const int my = next + rank;
-                next += __popcll(need);
-                if (!ray_active && my < total) {
-                    const int i = i_base + ((my & 63) >> 3), j = j_base + (my >> 6) * 16 + (my & 7);
-                    if (i < p.dim_in_0 && j < p.dim_in_1 && shadow_setup(p, i, j, p_sun_x, p_sun_y, p_sun_z, out_u8, out_f32, r)) {
-                        cell = (size_t)i * p.dim_in_1 + j;
-                        rb = hz_raybox((r.ox - p.sv.cx) - p.sv.tau * r.dx, (r.oy - p.sv.cy) - p.sv.tau * r.dy, (r.oz - p.sv.cz) - p.sv.tau * r.dz,
-                                       r.dx, r.dy, r.dz);
-                        hz_trav_reset(ts);
-                        overflow = false;
-                        ray_active = true;
-                        rays++;
-                    }
-                }
-            }
-        }
-        if (__ballot(ray_active) == 0ull) {
-            if (next >= total) break;
-            continue;
-        }
-        if (ray_active) {
-            int res = hz_trace<HZ_TPB, COUNT, 2, false, !FAST>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                    __builtin_inff(), __builtin_inff(), rb, ts, (next < total) ? HZ_SHADOW_REGROUP : 0, HZ_SHADOW_LEAF_BIAS, tc, p.stack_cap, overflow);
-            if (FAST && res != 2 && overflow) {
-                bool unused = false;
-                hz_trav_reset(ts);
-                res = hz_trace<HZ_TPB, COUNT, 2, false, true>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                                    __builtin_inff(), __builtin_inff(), rb, ts, 0, HZ_SHADOW_LEAF_BIAS, tc, 0, unused);
-                if (COUNT && p.counters) atomicAdd(&p.counters[HZ_SHADOW_CNT_TWICE], 1ull);
-            }
-            if (res != 2) {
-                accum_result(ap, cell, res == 1, r, out_u8, out_f32);
-                ray_active = false;
-            }
-        }
-    }
-    shadow_counters<COUNT>(p, rays, tc, lane);
+#define HZ_REFILL_PASS
+#define HZ_REFILL_BUSY ray_active
+#define HZ_REFILL_TAKE(i, j) \
+    if (shadow_setup(p, i, j, pos_x, pos_y, pos_z, out_u8, out_f32, r)) { cell = (size_t)i * p.dim_in_1 + j; HZ_REFILL_START_RAY(r); ray_active = true; }
+#define HZ_REFILL_PREPARE
+#define HZ_REFILL_TFAR __builtin_inff()
+#define HZ_REFILL_TFAR_BOX __builtin_inff()
+#define HZ_REFILL_REGROUP ((next < total) ? HZ_SHADOW_REGROUP : 0)
+#define HZ_REFILL_DECIDED(res) accum_result(ap, cell, res == 1, r, out_u8, out_f32); ray_active = false;
+#define HZ_REFILL_END
+#include "hz_refill_loop.inc"
 }
 
 int accum_trace_launch(const Scene *sc, const ShadowArgs &a, int want_sw, hipStream_t st) {
+    static void (*const kernels[2][2])(AccumParams) = HZ_REFILL_KERNELS(k_accum_refill);
     AccumParams ap;
     size_t lds = 0; dim3 grid; bool fast = false;
     if (!shadow_config(sc, a, ap.s, lds, grid, fast)) return HZ_OK;
     ap.want_sw = want_sw;
-    if (fast) { if (a.count_work) HZ_LAUNCH_REFILL((k_accum_refill<true, true>), ap); else HZ_LAUNCH_REFILL((k_accum_refill<false, true>), ap); }
-    else { if (a.count_work) HZ_LAUNCH_REFILL((k_accum_refill<true, false>), ap); else HZ_LAUNCH_REFILL((k_accum_refill<false, false>), ap); }
-    HZ_HIP(hipGetLastError());
-    return HZ_OK;
+    return refill_launch(kernels, ap, a.count_work, fast, grid, lds, st);
 }
-#undef HZ_LAUNCH_REFILL
 
 // One chunk of k positions into the accumulators, ascending in the position: acc += (double)w * (double)value, the product of
 // two floats exact in float64.  codes != null: the sunlit sum adds w * [code == 0], the correction sum w * (code == 0 ?

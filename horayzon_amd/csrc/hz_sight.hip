@@ -6,9 +6,9 @@
 // point to the observer, tfar = the distance.  The lane asks it for the top of the table, then for its bottom, then bisects
 // (hz_sight_search.h): up to 2 + ceil(log2(n - 1)) rays per cell.  Refraction is never applied.
 //
-// k_sight_refill is k_viewshed_refill's loop with one difference: a lane whose ray is decided advances its search and sets
-// up the next ray of the SAME cell; only a finished cell frees the lane for the hand-out.  It is a kernel of its own, in a
-// file of its own: the machine code of the other refill kernels must not move.
+// k_sight_refill is a __global__ of its own on the shared refill loop (as text, not a template: hz_refill_loop.inc), with one
+// difference to k_viewshed_refill: a lane whose ray is decided advances its search and sets up the next ray of the SAME
+// cell; only a finished cell frees the lane for the hand-out.
 #include "hz_internal.h"
 #include "hz_shadow.h"
 #include "hz_sight_search.h"
@@ -74,119 +74,61 @@ __device__ __forceinline__ void sight_result(const SightParams &vp, float *out, 
     }
 }
 
-// COUNT, FAST: as k_shadow_refill.  The traversal is the non-LEAN hz_trace with tfar and tfar_box per lane, as in
+// COUNT, FAST: hz_refill_loop.inc.  The traversal is the non-LEAN hz_trace with tfar and tfar_box per lane, as in
 // k_viewshed_refill.
 template <bool COUNT, bool FAST>
 __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_SIGHT_WG) void k_sight_refill(SightParams vp) {
     const ShadowParams &p = vp.s;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int *stack = reinterpret_cast<int *>(smem + (FAST ? 2 * HZ_TPB * 4 : 0));
-    const int tid = threadIdx.x;
-    int ti = 0, tj = 0;
-    const bool has_tile = hz_tile_of_block(p.tm, blockIdx.x, &ti, &tj);
-    const int wave = tid >> 6, lane = tid & 63;
-    const int obs_idx = blockIdx.y;
-    const float p_x = p.suns[3 * obs_idx], p_y = p.suns[3 * obs_idx + 1], p_z = p.suns[3 * obs_idx + 2];
-    float *const out = p.out_f32 ? p.out_f32 + (size_t)obs_idx * p.out_stride : nullptr;
-    const int n = vp.n;
-    unsigned rays = 0;
-    TravCounters tc; tc.nodes = 0; tc.tris = 0; tc.w_nodes = 0; tc.w_leaves = 0;
-    const int i_base = ti * 16 + (wave >> 1) * 8, j_base = tj * (16 * p.nb) + (wave & 1) * 8;
-    const int total = has_tile ? 64 * p.nb : 0;
-    int next = 0;                                   // cells handed out so far (wave uniform)
-    unsigned tally = 0;                             // cells with a finite result so far (wave uniform: a scalar register)
-    bool reached = false;                           // this lane finished a cell with a finite result since the last tally
-    int ci = 0, cj = 0;                             // the lane's cell
-    int phase = SIGHT_IDLE;                         // SIGHT_IDLE: the lane has no cell; else a ray of its cell is set up or wanted
-    unsigned lohi = 0;                              // the search bracket (hz_sight_search.h)
-    int k = HZ_SIGHT_NONE;                          // the table index the lane's next ray aims at (>= 0) while it is not set up yet
+#define HZ_REFILL_OUTPUTS float *const out = HZ_REFILL_OUT_AT(p.out_f32); const int n = vp.n;
+#define HZ_REFILL_LANE \
+    unsigned tally = 0;                             /* cells with a finite result so far (wave uniform: a scalar register) */ \
+    bool reached = false;                           /* this lane finished a cell with a finite result since the last tally */ \
+    int ci = 0, cj = 0;                             /* the lane's cell */ \
+    int phase = SIGHT_IDLE;                         /* SIGHT_IDLE: the lane has no cell; else a ray of its cell is set up or wanted */ \
+    unsigned lohi = 0;                              /* the search bracket (hz_sight_search.h) */ \
+    int k = HZ_SIGHT_NONE;                          /* the table index the lane's next ray aims at (>= 0) while it is not set up yet */ \
     SightRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.tfar = 0.0f;
-    RayBox rb = hz_raybox(0, 0, 0, 0, 0, 1);
-    TravState ts; hz_trav_reset(ts);
-    bool overflow = false;
-    for (;;) {
-        // the lanes marked since the last pass, counted where the whole wave is here (not live across hz_trace)
-        tally += (unsigned)__popcll(__ballot(reached));
-        reached = false;
-        if (next < total) {
-            const unsigned long long need = __ballot(phase == SIGHT_IDLE);
-            if (need != 0ull) {
-                const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
-                const int my = next + rank;
-                next += __popcll(need);
-                if (phase == SIGHT_IDLE && my < total) {
-                    const int i = i_base + ((my & 63) >> 3), j = j_base + (my >> 6) * 16 + (my & 7);
-                    if (i < p.dim_in_0 && j < p.dim_in_1) {
-                        const size_t cell = (size_t)i * p.dim_in_1 + j;
-                        if (p.mask[cell] != 1) {
-                            if (out) out[cell] = __uint_as_float(HZ_SIGHT_NAN_BITS);
-                        } else {
-                            ci = i; cj = j;
-                            bool far = false;
-                            if (vp.has_max) {               // the range is judged at the lowest target point
-                                SightRay r0;
-                                (void)sight_ray(vp, i, j, 0, p_x, p_y, p_z, r0);
-                                far = r0.tfar > vp.max_dist;
-                            }
-                            k = far ? SIGHT_UNREACHED : sight_begin(phase, lohi, n);
-                        }
-                    }
-                }
-            }
-        }
-        // The next ray of every lane that wants one: of a cell just taken, or of the cell whose last ray was decided below.  A
-        // target point that is the observer is visible without a ray: the search moves on at once.
-        while (sight_is_index(k)) {
-            if (sight_ray(vp, ci, cj, k, p_x, p_y, p_z, r)) {
-                // (box tests start at -tau and end at tfar + tau: hz_common.h)
-                rb = hz_raybox((r.ox - p.sv.cx) - p.sv.tau * r.dx, (r.oy - p.sv.cy) - p.sv.tau * r.dy, (r.oz - p.sv.cz) - p.sv.tau * r.dz,
-                               r.dx, r.dy, r.dz);
-                hz_trav_reset(ts);
-                overflow = false;
-                rays++;
-                k = HZ_SIGHT_NONE;
-                break;
-            }
-            k = sight_advance(phase, lohi, n, true);
-        }
-        if (k != HZ_SIGHT_NONE) {                    // finished without a (further) ray: out of range, or the observer is a target point
-            sight_result(vp, out, (size_t)ci * p.dim_in_1 + cj, k, reached);
-            k = HZ_SIGHT_NONE;
-        }
-        if (__ballot(phase != SIGHT_IDLE) == 0ull) {
-            if (next >= total) break;
-            continue;
-        }
-        if (phase != SIGHT_IDLE) {
-            const float tfar_box = r.tfar + 2.0f * p.sv.tau;
-            int res = hz_trace<HZ_TPB, COUNT, 2, false, !FAST>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                    r.tfar, tfar_box, rb, ts, HZ_SIGHT_REGROUP, HZ_SHADOW_LEAF_BIAS, tc, p.stack_cap, overflow);
-            if (FAST && res != 2 && overflow) {
-                bool unused = false;
-                hz_trav_reset(ts);
-                res = hz_trace<HZ_TPB, COUNT, 2, false, true>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                                    r.tfar, tfar_box, rb, ts, 0, HZ_SHADOW_LEAF_BIAS, tc, 0, unused);
-                if (COUNT && p.counters) atomicAdd(&p.counters[HZ_SHADOW_CNT_TWICE], 1ull);     // rays traced twice
-            }
-            if (res != 2) {
-                k = sight_advance(phase, lohi, n, res != 1);
-                if (!sight_is_index(k)) {
-                    sight_result(vp, out, (size_t)ci * p.dim_in_1 + cj, k, reached);
-                    k = HZ_SIGHT_NONE;
-                }
-            }
-        }
+// the lanes marked since the last pass, counted where the whole wave is here (not live across hz_trace)
+#define HZ_REFILL_PASS tally += (unsigned)__popcll(__ballot(reached)); reached = false;
+#define HZ_REFILL_BUSY (phase != SIGHT_IDLE)
+// a masked cell is written at once; the range is judged at the lowest target point
+#define HZ_REFILL_TAKE(i, j) \
+    const size_t cell = (size_t)i * p.dim_in_1 + j; \
+    if (p.mask[cell] != 1) { \
+        if (out) out[cell] = __uint_as_float(HZ_SIGHT_NAN_BITS); \
+    } else { \
+        ci = i; cj = j; \
+        bool far = false; \
+        if (vp.has_max) { \
+            SightRay r0; \
+            (void)sight_ray(vp, i, j, 0, pos_x, pos_y, pos_z, r0); \
+            far = r0.tfar > vp.max_dist; \
+        } \
+        k = far ? SIGHT_UNREACHED : sight_begin(phase, lohi, n); \
     }
-    tally += (unsigned)__popcll(__ballot(reached));
-    if (lane == 0 && tally && vp.cells_reached) atomicAdd(&vp.cells_reached[obs_idx], (unsigned long long)tally);
-    shadow_counters<COUNT>(p, rays, tc, lane);
+// The next ray of every lane that wants one: of a cell just taken, or of the cell whose last ray was decided.  A target point
+// that is the observer is visible without a ray: the search moves on at once.  Then the lanes that finished without a
+// (further) ray: out of range, or the observer is a target point.
+#define HZ_REFILL_PREPARE \
+    while (sight_is_index(k)) { \
+        if (sight_ray(vp, ci, cj, k, pos_x, pos_y, pos_z, r)) { HZ_REFILL_START_RAY(r); k = HZ_SIGHT_NONE; break; } \
+        k = sight_advance(phase, lohi, n, true); \
+    } \
+    if (k != HZ_SIGHT_NONE) { sight_result(vp, out, (size_t)ci * p.dim_in_1 + cj, k, reached); k = HZ_SIGHT_NONE; }
+#define HZ_REFILL_TFAR r.tfar
+#define HZ_REFILL_TFAR_BOX (r.tfar + 2.0f * p.sv.tau)
+#define HZ_REFILL_REGROUP HZ_SIGHT_REGROUP
+#define HZ_REFILL_DECIDED(res) \
+    k = sight_advance(phase, lohi, n, res != 1); \
+    if (!sight_is_index(k)) { sight_result(vp, out, (size_t)ci * p.dim_in_1 + cj, k, reached); k = HZ_SIGHT_NONE; }
+#define HZ_REFILL_END \
+    tally += (unsigned)__popcll(__ballot(reached)); \
+    if (lane == 0 && tally && vp.cells_reached) atomicAdd(&vp.cells_reached[pos], (unsigned long long)tally);
+#include "hz_refill_loop.inc"
 }
 
-#define HZ_LAUNCH_REFILL(K, P) do { \
-        HZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(K, grid, dim3(HZ_TPB), lds, st, P); } while (0)
-
 int sight_launch(const Scene *sc, const ShadowArgs &a, const SightArgs &v, hipStream_t st) {
+    static void (*const kernels[2][2])(SightParams) = HZ_REFILL_KERNELS(k_sight_refill);
     SightParams vp;
     size_t lds = 0; dim3 grid; bool fast = false;
     if (v.num_heights < 1 || v.num_heights > 65535 || !v.heights) return set_error(HZ_ERR_ARG, "sight_launch: bad height table");
@@ -195,12 +137,8 @@ int sight_launch(const Scene *sc, const ShadowArgs &a, const SightArgs &v, hipSt
     vp.max_dist = v.max_dist; vp.has_max = v.has_max;
     vp.lowest = reinterpret_cast<unsigned *>(v.lowest);
     vp.cells_reached = reinterpret_cast<unsigned long long *>(v.cells_reached);
-    if (fast) { if (a.count_work) HZ_LAUNCH_REFILL((k_sight_refill<true, true>), vp); else HZ_LAUNCH_REFILL((k_sight_refill<false, true>), vp); }
-    else { if (a.count_work) HZ_LAUNCH_REFILL((k_sight_refill<true, false>), vp); else HZ_LAUNCH_REFILL((k_sight_refill<false, false>), vp); }
-    HZ_HIP(hipGetLastError());
-    return HZ_OK;
+    return refill_launch(kernels, vp, a.count_work, fast, grid, lds, st);
 }
-#undef HZ_LAUNCH_REFILL
 
 // before the first launch of a call: every cell of `lowest` holds the bits of +inf, the neutral element of the minimum
 __global__ __launch_bounds__(256) void k_sight_lowest_init(size_t n, unsigned *__restrict__ lowest) {

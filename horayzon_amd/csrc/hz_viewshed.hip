@@ -5,9 +5,8 @@
 // tfar = the distance to it: unlike a sun position the observer is a point of the scene's frame, and terrain behind it
 // blocks nothing.  Refraction is never applied.
 //
-// k_viewshed_refill is k_shadow_refill's loop (hz_shadow.hip) with a set-up and a result step of its own and a tfar per
-// lane.  It is a kernel of its own, as k_accum_refill is: k_shadow_refill<false, true> stamps profiles/*.json and its machine
-// code must not move.
+// k_viewshed_refill is a __global__ of its own on the shared refill loop, with a set-up and a result step of its own and a
+// tfar per lane (why the loop is shared as text and not as a template: hz_refill_loop.inc).
 #include "hz_internal.h"
 #include "hz_shadow.h"
 
@@ -67,106 +66,46 @@ __device__ __forceinline__ void viewshed_result(const ViewshedParams &vp, uint8_
     }
 }
 
-// COUNT, FAST: as k_shadow_refill.  The traversal is the non-LEAN hz_trace, which reads tfar and tfar_box per lane (only the
+// COUNT, FAST: hz_refill_loop.inc.  The traversal is the non-LEAN hz_trace, which reads tfar and tfar_box per lane (only the
 // LEAN form keeps tfar in a scalar register, hz_min_uniform): a wave's 64 rays end at 64 different distances.
 template <bool COUNT, bool FAST>
 __global__ __launch_bounds__(HZ_TPB, COUNT ? 5 : HZ_VIEWSHED_WG) void k_viewshed_refill(ViewshedParams vp) {
     const ShadowParams &p = vp.s;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int *stack = reinterpret_cast<int *>(smem + (FAST ? 2 * HZ_TPB * 4 : 0));
-    const int tid = threadIdx.x;
-    int ti = 0, tj = 0;
-    const bool has_tile = hz_tile_of_block(p.tm, blockIdx.x, &ti, &tj);
-    const int wave = tid >> 6, lane = tid & 63;
-    const int obs_idx = blockIdx.y;
-    const float p_x = p.suns[3 * obs_idx], p_y = p.suns[3 * obs_idx + 1], p_z = p.suns[3 * obs_idx + 2];
-    uint8_t *const out_u8 = p.out_u8 ? p.out_u8 + (size_t)obs_idx * p.out_stride : nullptr;
-    unsigned rays = 0;
-    TravCounters tc; tc.nodes = 0; tc.tris = 0; tc.w_nodes = 0; tc.w_leaves = 0;
-    const int i_base = ti * 16 + (wave >> 1) * 8, j_base = tj * (16 * p.nb) + (wave & 1) * 8;
-    const int total = has_tile ? 64 * p.nb : 0;
-    int next = 0;                                   // cells handed out so far (wave uniform)
-    unsigned tally = 0;                             // cells with code 0 so far (wave uniform: a scalar register)
-    bool seen = false;                              // this lane decided a code 0 since the last tally
-    bool ray_active = false;
-    ViewRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.tfar = 0.0f;
+#define HZ_REFILL_OUTPUTS uint8_t *const out_u8 = HZ_REFILL_OUT_AT(p.out_u8);
+#define HZ_REFILL_LANE \
+    unsigned tally = 0;                             /* cells with code 0 so far (wave uniform: a scalar register) */ \
+    bool seen = false;                              /* this lane decided a code 0 since the last tally */ \
+    bool ray_active = false; \
+    ViewRay r; r.ox = r.oy = r.oz = 0.0f; r.dx = r.dy = 0.0f; r.dz = 1.0f; r.tfar = 0.0f; \
     size_t cell = 0;
-    RayBox rb = hz_raybox(0, 0, 0, 0, 0, 1);
-    TravState ts; hz_trav_reset(ts);
-    bool overflow = false;
-    for (;;) {
-        // the lanes marked since the last pass, counted where the whole wave is here (not live across hz_trace)
-        tally += (unsigned)__popcll(__ballot(seen));
-        seen = false;
-        if (next < total) {
-            const unsigned long long need = __ballot(!ray_active);
-            if (need != 0ull) {
-                const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
-                const int my = next + rank;
-                next += __popcll(need);
-                if (!ray_active && my < total) {
-                    const int i = i_base + ((my & 63) >> 3), j = j_base + (my >> 6) * 16 + (my & 7);
-                    if (i < p.dim_in_0 && j < p.dim_in_1) {
-                        const int code = viewshed_setup(vp, i, j, p_x, p_y, p_z, r);
-                        if (code == HZ_VIEW_RAY) {
-                            cell = (size_t)i * p.dim_in_1 + j;
-                            // (box tests start at -tau and end at tfar + tau: hz_common.h)
-                            rb = hz_raybox((r.ox - p.sv.cx) - p.sv.tau * r.dx, (r.oy - p.sv.cy) - p.sv.tau * r.dy, (r.oz - p.sv.cz) - p.sv.tau * r.dz,
-                                           r.dx, r.dy, r.dz);
-                            hz_trav_reset(ts);
-                            overflow = false;
-                            ray_active = true;
-                            rays++;
-                        } else {
-                            viewshed_result(vp, out_u8, (size_t)i * p.dim_in_1 + j, code, seen);
-                        }
-                    }
-                }
-            }
-        }
-        if (__ballot(ray_active) == 0ull) {
-            if (next >= total) break;
-            continue;
-        }
-        if (ray_active) {
-            const float tfar_box = r.tfar + 2.0f * p.sv.tau;
-            int res = hz_trace<HZ_TPB, COUNT, 2, false, !FAST>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                    r.tfar, tfar_box, rb, ts, (next < total) ? HZ_SHADOW_REGROUP : 0, HZ_SHADOW_LEAF_BIAS, tc, p.stack_cap, overflow);
-            if (FAST && res != 2 && overflow) {
-                bool unused = false;
-                hz_trav_reset(ts);
-                res = hz_trace<HZ_TPB, COUNT, 2, false, true>(p.sv.nodes, p.sv.prims, nullptr, 0, stack, tid, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                                    r.tfar, tfar_box, rb, ts, 0, HZ_SHADOW_LEAF_BIAS, tc, 0, unused);
-                if (COUNT && p.counters) atomicAdd(&p.counters[HZ_SHADOW_CNT_TWICE], 1ull);     // rays traced twice
-            }
-            if (res != 2) {
-                viewshed_result(vp, out_u8, cell, res == 1 ? 2 : 0, seen);
-                ray_active = false;
-            }
-        }
-    }
-    tally += (unsigned)__popcll(__ballot(seen));
-    if (lane == 0 && tally && vp.cells_seen) atomicAdd(&vp.cells_seen[obs_idx], (unsigned long long)tally);
-    shadow_counters<COUNT>(p, rays, tc, lane);
+// the lanes marked since the last pass, counted where the whole wave is here (not live across hz_trace)
+#define HZ_REFILL_PASS tally += (unsigned)__popcll(__ballot(seen)); seen = false;
+#define HZ_REFILL_BUSY ray_active
+#define HZ_REFILL_TAKE(i, j) \
+    const int code = viewshed_setup(vp, i, j, pos_x, pos_y, pos_z, r); \
+    if (code == HZ_VIEW_RAY) { cell = (size_t)i * p.dim_in_1 + j; HZ_REFILL_START_RAY(r); ray_active = true; } \
+    else viewshed_result(vp, out_u8, (size_t)i * p.dim_in_1 + j, code, seen);
+#define HZ_REFILL_PREPARE
+#define HZ_REFILL_TFAR r.tfar
+#define HZ_REFILL_TFAR_BOX (r.tfar + 2.0f * p.sv.tau)
+#define HZ_REFILL_REGROUP ((next < total) ? HZ_SHADOW_REGROUP : 0)
+#define HZ_REFILL_DECIDED(res) viewshed_result(vp, out_u8, cell, res == 1 ? 2 : 0, seen); ray_active = false;
+#define HZ_REFILL_END \
+    tally += (unsigned)__popcll(__ballot(seen)); \
+    if (lane == 0 && tally && vp.cells_seen) atomicAdd(&vp.cells_seen[pos], (unsigned long long)tally);
+#include "hz_refill_loop.inc"
 }
 
-#define HZ_LAUNCH_REFILL(K, P) do { \
-        HZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(K, grid, dim3(HZ_TPB), lds, st, P); } while (0)
-
 int viewshed_launch(const Scene *sc, const ShadowArgs &a, const ViewshedArgs &v, hipStream_t st) {
+    static void (*const kernels[2][2])(ViewshedParams) = HZ_REFILL_KERNELS(k_viewshed_refill);
     ViewshedParams vp;
     size_t lds = 0; dim3 grid; bool fast = false;
     if (!shadow_config(sc, a, vp.s, lds, grid, fast)) return HZ_OK;
     vp.target_elev = v.target_elev; vp.max_dist = v.max_dist; vp.has_max = v.has_max; vp.facing = v.facing;
     vp.seen_count = v.seen_count;
     vp.cells_seen = reinterpret_cast<unsigned long long *>(v.cells_seen);
-    if (fast) { if (a.count_work) HZ_LAUNCH_REFILL((k_viewshed_refill<true, true>), vp); else HZ_LAUNCH_REFILL((k_viewshed_refill<false, true>), vp); }
-    else { if (a.count_work) HZ_LAUNCH_REFILL((k_viewshed_refill<true, false>), vp); else HZ_LAUNCH_REFILL((k_viewshed_refill<false, false>), vp); }
-    HZ_HIP(hipGetLastError());
-    return HZ_OK;
+    return refill_launch(kernels, vp, a.count_work, fast, grid, lds, st);
 }
-#undef HZ_LAUNCH_REFILL
 
 // after the last launch of a call: masked cells (mask != 1) count -1 observers, whatever was added there (nothing)
 __global__ __launch_bounds__(256) void k_viewshed_masked(const uint8_t *__restrict__ mask, size_t n, int *__restrict__ seen_count) {

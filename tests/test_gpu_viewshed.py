@@ -9,28 +9,13 @@ import pytest
 from horayzon_amd import synth
 from tests import cases
 from tests import viewshed_reference as vr
+from tests.debug_knobs import fast_cap
 from tests.test_viewshed_reference import MAX_DIST, fixture, near_observers
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX_POS = 32768          # observers of one launch (hz_api_sun.hip: HZ_SHADOW_MAX_POS, grid.y)
-
-
-class fast_cap:
-    """hz_debug_set("shadow_fast_cap", n) for the block, the default restored afterwards."""
-
-    def __init__(self, n):
-        self.n = n
-
-    def __enter__(self):
-        from horayzon_amd import _lib
-        _lib.check(_lib.lib().hz_debug_set(b"shadow_fast_cap", self.n))
-
-    def __exit__(self, *exc):
-        from horayzon_amd import _lib
-        _lib.check(_lib.lib().hz_debug_set(b"shadow_fast_cap", -1))
-        return False
 
 
 def six_observers(g):
