@@ -95,7 +95,7 @@ SYMBOLS = (
     "hz_terrain_shadow", "hz_terrain_sw_dir_cor", "hz_terrain_shadow_batch",
     "hz_terrain_sw_dir_cor_batch", "hz_terrain_count_work", "hz_terrain_destroy",
     "hz_terrain_accumulate", "hz_terrain_sw_dir_cor_coarse", "hz_terrain_viewshed", "hz_terrain_sight_height",
-    "hz_terrain_panorama",
+    "hz_terrain_panorama", "hz_terrain_cast",
     "hz_coastline_distance", "hz_coastline_buffer",
     "hz_horizon_terrain_create", "hz_horizon_terrain_initialise", "hz_horizon_terrain_run", "hz_horizon_terrain_destroy",
     "hz_horizon_gridded_planes", "hz_horizon_gridded_scene_planes", "hz_hori_to_planes", "hz_hori_from_planes",
@@ -232,6 +232,7 @@ def lib():
     L.hz_terrain_viewshed.argtypes = [vp, vp, ip, C.c_float, C.c_float, ip, vp, vp, vp, C.POINTER(hz_stats)]
     L.hz_terrain_sight_height.argtypes = [vp, vp, ip, vp, ip, C.c_float, vp, vp, vp, C.POINTER(hz_stats)]
     L.hz_terrain_panorama.argtypes = [vp, vp, ip, vp, vp, ip, vp, vp, ip, vp, vp, C.c_float, vp, vp, vp, C.POINTER(hz_stats)]
+    L.hz_terrain_cast.argtypes = [vp, vp, vp, vp, ip, C.c_float, ip, vp, vp, vp, C.POINTER(hz_stats)]
     L.hz_terrain_count_work.argtypes = [vp, ip]
     L.hz_coastline_distance.argtypes = [vp, vp, vp, vp, ip, ip, vp, C.c_size_t, vp, ip, C.POINTER(hz_stats)]
     L.hz_coastline_buffer.argtypes = [vp, vp, vp, vp, ip, ip, vp, C.c_size_t, C.c_double, vp, ip, C.POINTER(hz_stats)]

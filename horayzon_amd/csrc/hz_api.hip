@@ -519,6 +519,9 @@ int hz_debug_set(const char *key, int value) {
         hz::g_panorama_traversal.store(value, std::memory_order_relaxed);
     }
     else if (!strcmp(key, "panorama_budget")) hz::g_panorama_budget.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "cast_budget")) hz::g_cast_budget.store(value < 0 ? 0 : value, std::memory_order_relaxed);
+    else if (!strcmp(key, "cast_sort_only")) hz::g_cast_sort_only.store(value > 0 ? 1 : 0, std::memory_order_relaxed);
+    else if (!strcmp(key, "cast_fast_cap")) hz::g_cast_fast_cap.store(value < 0 ? HZ_CAST_FAST_CAP_DEFAULT : value, std::memory_order_relaxed);
     else return hz::set_error(HZ_ERR_ARG, "hz_debug_set: unknown key '%s'", key);
     return HZ_OK;
 }

@@ -2,14 +2,15 @@
 // Terrain (hz_terrain_*: rays against the scene, restating CppTerrain, shadow_comp.cpp:304-605) and HorizonTerrain
 // (hz_horizon_terrain_*: look-ups in a stored horizon).
 //
-// Nine calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
-// hz_terrain_viewshed, hz_terrain_sight_height, hz_terrain_panorama, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
+// Ten calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
+// hz_terrain_viewshed, hz_terrain_sight_height, hz_terrain_panorama, hz_terrain_cast, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
 // allocations, one chunk loop with the launches, finish; what they share -- device, lock, stream, timers, the scratch tally,
 // staged inputs, staged outputs -- is SunCall and ChunkFeed below.
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
 #include "hz_horisun_coarse_plan.h"
 #include "hz_panorama_plan.h"
+#include "hz_cast_plan.h"
 #include <cmath>
 #include <vector>
 #include <mutex>
@@ -747,6 +748,82 @@ int hz_terrain_panorama(hz_terrain *terrain, const float *observers, int num_obs
         stats->num_rays += (unsigned long long)num_obs * plan.pixels;      // every pixel is one ray
         stats->scratch_bytes = call.scratch;
     }
+    return HZ_OK;
+}
+
+// Terrain.cast (hz_cast.hip: k_cast_closest, k_cast_any, k_cast_keys; DESIGN.md section 4 clause 21).  The rays go in chunks
+// (hz_cast_plan.h): origins and directions / targets given as host memory go up one chunk at a time, outputs given as host
+// memory are staged one chunk at a time and copied out inside the loop, and order = 1 sorts the chunk's (key, ray number)
+// pairs on the device; all of that -- what hz_stats.scratch_bytes reports -- is held to the budget and does not grow with
+// num_rays.  Device arrays are read and written in place.  The copies are not overlapped with the tracing.
+int hz_terrain_cast(hz_terrain *terrain, const float *origins, const float *directions, const float *targets, int num_rays,
+                    float max_dist, int order, uint8_t *occluded, float *dist, float *point, hz_stats *stats) {
+    Terrain *t = reinterpret_cast<Terrain *>(terrain);
+    if (!t || !t->initialised) return set_error(HZ_ERR_ARG, "Terrain is not initialised");
+    if (!origins || num_rays < 1 || (long long)num_rays > HZ_CAST_MAX_RAYS) return set_error(HZ_ERR_ARG, "array 'origins' has incorrect shape");
+    if ((directions == nullptr) == (targets == nullptr)) return set_error(HZ_ERR_ARG, "exactly one of 'directions' and 'targets' must be given");
+    if (directions && (!std::isfinite(max_dist) || !(max_dist > 0.0f))) return set_error(HZ_ERR_ARG, "'max_dist' must be finite and greater than 0");
+    if (order != 0 && order != 1) return set_error(HZ_ERR_ARG, "'order' is 0 (given) or 1 (sorted)");
+    if (!occluded && !dist && !point) return set_error(HZ_ERR_ARG, "no output buffer (occluded, dist and point are NULL)");
+    const void *outs[3] = {occluded, dist, point};
+    int rc;
+    if ((rc = check_distinct_outputs(outs, 3))) return rc;
+    const float *ends_src = directions ? directions : targets;
+    const bool stage_occ = occluded && !is_device_ptr(occluded), stage_dist = dist && !is_device_ptr(dist),
+               stage_point = point && !is_device_ptr(point);
+    ChunkFeed<float> org(origins, 3), ends(ends_src, 3);
+    const int knob = g_cast_budget.load(std::memory_order_relaxed);           // (hz_debug_set("cast_budget", bytes): tests)
+    CastPlan plan;
+    if (!cast_plan(num_rays, org.staged(), ends.staged(), stage_occ, stage_dist, stage_point, order == 1,
+                   knob > 0 ? (unsigned long long)knob : HZ_CAST_BUDGET, &plan))
+        return set_error(HZ_ERR_ARG, "cast: no plan for %d rays", num_rays);
+    SunCall call;
+    if ((rc = call.start(t->device, t->scene->run_mu, t->stream))) return rc;
+    const int k = plan.chunk;
+    if ((rc = org.staged() && ends.staged() ? call.stage(k, org, ends) : org.staged() ? call.stage(k, org) : call.stage(k, ends))) return rc;
+    // a staged output holds one chunk; an output in device memory is the caller's whole array
+    DevOut<uint8_t> d_occ; DevOut<float> d_dist, d_point;
+    if ((rc = call.bind(d_occ, occluded, stage_occ ? (size_t)k : (size_t)num_rays, true)) ||
+        (rc = call.bind(d_dist, dist, stage_dist ? (size_t)k : (size_t)num_rays, true)) ||
+        (rc = call.bind(d_point, point, 3 * (stage_point ? (size_t)k : (size_t)num_rays), true)))
+        return rc;
+    // order = 1: keys and ray numbers, in and out, and the sort's histograms
+    DevBuf sort_buf;
+    uint32_t *keys_a = nullptr, *vals_a = nullptr, *keys_b = nullptr, *vals_b = nullptr, *sort_tmp = nullptr;
+    if (order == 1) {
+        if ((rc = call.alloc(sort_buf, (4 * (size_t)k + sort_temp_elems((size_t)k)) * sizeof(uint32_t)))) return rc;
+        keys_a = static_cast<uint32_t *>(sort_buf.p); vals_a = keys_a + k; keys_b = vals_a + k; vals_b = keys_b + k; sort_tmp = vals_b + k;
+    }
+    CastArgs a;
+    a.segments = targets ? 1 : 0; a.max_dist = max_dist; a.perm = nullptr;
+    a.counters = t->counters; a.count_work = t->count_work;
+    const bool trace = g_cast_sort_only.load(std::memory_order_relaxed) == 0;
+    if ((rc = terrain_begin(t, call))) return rc;
+    for (long long s0 = 0; s0 < (long long)num_rays; s0 += k) {
+        const int kc = (int)std::min<long long>(k, (long long)num_rays - s0);
+        if ((rc = org.at((int)s0, kc, call.st, &a.origins)) || (rc = ends.at((int)s0, kc, call.st, &a.ends))) return rc;
+        a.num_rays = (unsigned)kc;
+        if (order == 1) {
+            if ((rc = cast_keys_launch(t->scene, a.origins, a.ends, a.segments, a.num_rays, keys_a, vals_a, call.st)) ||
+                (rc = radix_sort_pairs_u32(keys_a, vals_a, keys_b, vals_b, (size_t)kc, sort_tmp, call.st, 4)))      // 4 passes: sorted in vals_a
+                return rc;
+            a.perm = vals_a;
+        }
+        if (!trace) continue;
+        a.occluded = d_occ.dev ? d_occ.dev + (stage_occ ? 0 : (size_t)s0) : nullptr;
+        a.dist = d_dist.dev ? d_dist.dev + (stage_dist ? 0 : (size_t)s0) : nullptr;
+        a.point = d_point.dev ? d_point.dev + (stage_point ? 0 : 3 * (size_t)s0) : nullptr;
+        if ((rc = cast_launch(t->scene, a, call.st))) return rc;
+        // the chunk's staged results go out before the next chunk is traced into the same memory (stream order)
+        if (stage_occ) HZ_HIP(hipMemcpyAsync(occluded + (size_t)s0, d_occ.dev, (size_t)kc, hipMemcpyDeviceToHost, call.st));
+        if (stage_dist) HZ_HIP(hipMemcpyAsync(dist + (size_t)s0, d_dist.dev, (size_t)kc * sizeof(float), hipMemcpyDeviceToHost, call.st));
+        if (stage_point) HZ_HIP(hipMemcpyAsync(point + 3 * (size_t)s0, d_point.dev, 3 * (size_t)kc * sizeof(float), hipMemcpyDeviceToHost, call.st));
+    }
+    unsigned long long cnt[HZ_SHADOW_CNT_N];
+    if ((rc = terrain_end(t, call, cnt))) return rc;
+    if ((rc = call.finish(stats))) return rc;
+    terrain_stats(t, cnt, stats);                   // num_rays: the rays the kernels traced
+    if (stats) stats->scratch_bytes = call.scratch;
     return HZ_OK;
 }
 

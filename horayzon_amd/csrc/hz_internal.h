@@ -486,6 +486,32 @@ int panorama_launch(const Scene *sc, const PanoramaArgs &a, hipStream_t st);
 extern std::atomic<int> g_panorama_traversal;   // "panorama_traversal" (hz_debug_set): 0 hz_closest's slot order, 1 (default, also < 0) the children of a node front to back
 extern std::atomic<int> g_panorama_budget;      // "panorama_budget" (hz_debug_set): > 0 bytes of staged output per chunk of hz_terrain_panorama (default 0: HZ_PANORAMA_BUDGET)
 
+// hz_cast.hip (hz_terrain_cast; device pointers; DESIGN.md section 4, clause 21): one launch over the num_rays rays of a chunk
+// (at most HZ_CAST_MAX_CHUNK, hz_cast_plan.h).  origins f32[num_rays][3]; ends f32[num_rays][3]: unit directions of length
+// max_dist, or (segments) the targets the rays end at.  perm u32[num_rays] or null: the launch traces the rays in the order
+// perm[0], perm[1], ... (a permutation of 0 ... num_rays - 1).  The outputs start at the chunk's first ray: occluded
+// u8[num_rays], dist f32[num_rays], point f32[num_rays][3]; null: not wanted.  dist or point: k_cast_closest; occluded alone:
+// k_cast_any (count_work: its counting instantiation).  counters[HZ_SHADOW_CNT_RAYS] += the rays traced.
+struct CastArgs {
+    const float *origins, *ends;
+    const uint32_t *perm;
+    unsigned num_rays;
+    int segments;
+    float max_dist;
+    uint8_t *occluded;
+    float *dist, *point;
+    unsigned long long *counters;
+    int count_work;
+};
+int cast_launch(const Scene *sc, const CastArgs &a, hipStream_t st);
+// keys[i] = the sort key of ray i of the chunk (origin's Morton code over the scene's box, direction code), vals[i] = i
+int cast_keys_launch(const Scene *sc, const float *origins, const float *ends, int segments, unsigned num_rays, uint32_t *keys,
+                     uint32_t *vals, hipStream_t st);
+#define HZ_CAST_FAST_CAP_DEFAULT 19             // entries of k_cast_any's fast stack (k_shadow_refill's value)
+extern std::atomic<int> g_cast_budget;          // "cast_budget" (hz_debug_set): > 0 bytes of staging and sort memory per chunk of hz_terrain_cast (default 0: HZ_CAST_BUDGET)
+extern std::atomic<int> g_cast_sort_only;       // "cast_sort_only" (hz_debug_set): 1 = hz_terrain_cast stops after the keys and the sort of every chunk and writes no output (scripts/cast_perf.py times them alone)
+extern std::atomic<int> g_cast_fast_cap;        // "cast_fast_cap" (hz_debug_set): entries of k_cast_any's fast stack (default HZ_CAST_FAST_CAP_DEFAULT; 0: level stack only)
+
 // hz_horisun_coarse.hip (hz_horizon_terrain_sw_dir_cor_coarse; device pointers): the plan of the fused kernel for chunks of
 // up to `chunk` positions (hz_horisun_coarse_plan.h; plan->fallback = 1: the shape, the "horisun_coarse_route" knob or the layout's default asks
 // for the two-pass route), and one launch of k_horisun_coarse over the a.num_sun <= chunk positions of a chunk: block means

@@ -455,6 +455,91 @@ class Terrain:
             ptr(dist), ptr(point), ptr(hits), C.byref(st)))
         self.last_stats = st.as_dict()
 
+    # --- additive: any-hit and closest-hit for the caller's own rays ----------------------------------------------------
+    def cast(self, origins, directions=None, *, targets=None, max_dist=None, occluded=None, dist=None, point=None,
+             order="given"):
+        """Traces rays the caller supplies against the whole scene (clause 21): intervisibility of
+        point pairs, a sensor's view vector per cell, the pixels of a camera model, a scan pattern.  origins f32[N][3] in
+        the scene's frame (that of ``observers`` in ``viewshed``), 1 <= N <= 2**31 - 64, and exactly one of
+        ``directions`` f32[N][3], unit vectors (used as given, not normalised) with ``max_dist`` [m] the length of every
+        ray (a number, finite and > 0 as float32), or ``targets`` f32[N][3], the far end of a segment (``max_dist`` must
+        then be None): the ray runs from the origin to the target and terrain behind the target blocks nothing; a target on
+        its origin gives no ray (``occluded`` 0, ``dist`` and ``point`` NaN).  Inputs are NumPy arrays or torch tensors on
+        the Terrain's GPU, C-contiguous and finite.  Outputs, any subset, at least one, distinct buffers, every element
+        written: ``occluded`` u8[N] 1 if any triangle is hit within the ray, else 0; ``dist`` f32[N] the distance to the
+        closest triangle, NaN where nothing is hit (an origin on the surface hits it at 0.0); ``point`` f32[N][3] the hit
+        point origin + direction * dist (NaN x 3 where nothing is hit); NumPy or torch tensors on the Terrain's GPU.
+        ``occluded`` alone runs an any-hit kernel that stops at the first triangle; it gives the byte the closest-hit
+        kernel gives.  ``mask``, ``vec_tilt`` and the inner-domain offsets play no part and refraction is never applied.
+        ``order``: "given" traces the rays in the caller's order, "sorted" traces each chunk in an order computed on the
+        device (a radix sort of origin and direction codes); the results never depend on it.  The sort costs 0.06 ns per
+        ray on an MI355X.  Measured on a 3601 x 3601 tile it paid in one case only: closest-hit rays
+        (``dist`` / ``point``) in random order whose origins lie all over the terrain, 20 % faster.  It did not pay for
+        ``occluded`` alone (18 % slower), for rays from a handful of origins in any order (33 % slower), or for rays that
+        already follow one another in memory the way they do in space.  ``last_stats["num_rays"]`` is the number
+        of rays traced: N minus the degenerate segments.  Rays go in chunks: NumPy inputs and outputs are staged on the
+        device one chunk at a time and the sort works on one chunk (together at most 256 MiB, plus the sort's histograms), so
+        ``last_stats["scratch_bytes"]`` does not grow with N; the copies are not overlapped with the tracing.  The
+        finiteness and unit-length checks of inputs given as tensors read reductions back from the GPU: one device
+        synchronisation each per call before the launches.  Not offered: a ``max_dist`` per ray, the triangle or cell that
+        was hit, one origin shared by all rays, more than one GPU."""
+        outs = (("occluded", occluded, 1, np.uint8), ("dist", dist, 1, np.float32), ("point", point, 2, np.float32))
+        ends = [(name, v) for name, v in (("directions", directions), ("targets", targets)) if v is not None]
+        self._array_arg(origins, 2, "origins")
+        for name, v in ends:
+            self._array_arg(v, 2, name)
+        if max_dist is not None and (not isinstance(max_dist, (int, float, np.integer, np.floating)) or
+                                     isinstance(max_dist, (bool, np.bool_))):
+            raise TypeError("Argument 'max_dist' has incorrect type (expected a number, got %s)" % type(max_dist).__name__)
+        for name, buf, ndim, dtype in outs:
+            if buf is not None:
+                self._array_arg(buf, ndim, name, dtype)
+        given = [buf for _, buf, _, _ in outs if buf is not None]
+
+        def finite(a):
+            if _is_tensor(a):
+                import torch
+                return bool(torch.isfinite(a).all().item())
+            return bool(np.isfinite(a).all())
+
+        def unit(v):
+            if _is_tensor(v):
+                return float(((v * v).sum(dim=1) - 1.0).abs().max().item()) <= 1.0e-5
+            return V.unit_vectors(v[None])
+        with np.errstate(over="ignore"):
+            tfar = np.float32(0.0 if max_dist is None else max_dist)         # the ray length the kernel sees
+        n = lambda: origins.shape[0]                                          # noqa: E731
+        V.run((
+            (ValueError, "exactly one of 'directions' and 'targets' must be given", lambda: len(ends) != 1),
+            (ValueError, "'max_dist' must be given with 'directions'", lambda: directions is not None and max_dist is None),
+            (ValueError, "'max_dist' must be None with 'targets'", lambda: targets is not None and max_dist is not None),
+            (ValueError, "at least one of 'occluded', 'dist' and 'point' must be given", lambda: not given),
+            (ValueError, "'order' must be 'given' or 'sorted'", lambda: not isinstance(order, str) or order not in ("given", "sorted")),
+            (ValueError, "array 'origins' has incorrect shape", lambda: origins.shape[1] != 3 or n() < 1),
+            (ValueError, "'origins' must not have more than 2**31 - 64 rays", lambda: n() > 2 ** 31 - 64),
+            (ValueError, "array '%s' has incorrect shape" % ends[0][0] if ends else "",
+             lambda: tuple(ends[0][1].shape) != (n(), 3)),
+            (ValueError, "array 'occluded' has incorrect shape", lambda: occluded is not None and tuple(occluded.shape) != (n(),)),
+            (ValueError, "array 'dist' has incorrect shape", lambda: dist is not None and tuple(dist.shape) != (n(),)),
+            (ValueError, "array 'point' has incorrect shape", lambda: point is not None and tuple(point.shape) != (n(), 3)),
+            (ValueError, "not all input arrays are C-contiguous",
+             lambda: not all(_contiguous(a) for a in [origins, ends[0][1]] + given)),
+            (ValueError, "'occluded', 'dist' and 'point' must be different arrays",
+             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            (ValueError, "'max_dist' must be finite and greater than 0",
+             lambda: directions is not None and not (np.isfinite(tfar) and tfar > 0)),
+            (ValueError, "array 'origins' has non-finite entries", lambda: not finite(origins)),
+            (ValueError, "array '%s' has non-finite entries" % ends[0][0] if ends else "", lambda: not finite(ends[0][1])),
+            (ValueError, "Vectors in 'directions' are not normalised", lambda: directions is not None and not unit(directions)),
+        ))
+        if self._shape is None:
+            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
+        st = hz_stats()
+        _lib.check(_lib.lib().hz_terrain_cast(
+            self._h, ptr(origins), ptr(directions), ptr(targets), origins.shape[0], float(tfar),
+            1 if order == "sorted" else 0, ptr(occluded), ptr(dist), ptr(point), C.byref(st)))
+        self.last_stats = st.as_dict()
+
     # --- additive: the lowest target height in sight, per observer and cell --------------------------------------------
     def sight_height(self, observers, heights, *, height=None, lowest=None, cells_reached=None, max_dist=None):
         """How high above each cell a target must be to have a free line of sight to each point of observers f32[S][3]

@@ -667,6 +667,29 @@ int hz_terrain_panorama(hz_terrain *terrain, const float *observers, int num_obs
                         const float *elev_sin, const float *elev_cos, int elev_num,
                         const float *vec_north, const float *vec_norm,   /* both NULL: planar frame */
                         float max_dist, float *dist, float *point, int64_t *hits, hz_stats *stats);
+/* additive: any-hit and closest-hit for rays the caller supplies (DESIGN.md section 4 clause 21).  origins f32[num_rays][3] in */
+/* the scene's frame (as observers of hz_terrain_viewshed), 1 <= num_rays <= 2^31 - 64, and exactly one of                      */
+/*   directions f32[num_rays][3]: unit vectors, used as given (not normalised); ray i = (origins[i], directions[i], tfar =      */
+/*     max_dist), max_dist finite and > 0;                                                                                      */
+/*   targets f32[num_rays][3]: d = target - origin, mag = sqrtf((dx dx + dy dy) + dz dz); !(mag > 0): no ray -- occluded 0,      */
+/*     dist and point NaN, not counted; else ray i = (origins[i], d / mag, tfar = mag).  max_dist is not read.                  */
+/* All float32, every product, sum, square root and quotient rounded on its own.  Per ray:                                      */
+/*   occluded[i] = 1 if a triangle is accepted within the ray, else 0;  dist[i] = the minimum t over all accepted triangles,    */
+/*   NaN if there is none (a minimum that is zero is written as +0.0);  point[i][c] = origin[c] + dir[c] * dist[i] (NaN x 3).   */
+/* occluded u8[num_rays], dist f32[num_rays], point f32[num_rays][3]; NULL = not wanted (at least one; they must differ); every */
+/* element is written.  occluded alone runs an any-hit kernel that stops at the first accepted triangle; it is the byte the     */
+/* closest-hit kernel writes.  order 0: the rays are traced in the caller's order; 1: each chunk in an order computed on the   */
+/* device (a radix sort of origin and direction codes) -- the results do not depend on it.  Every pointer may be host or        */
+/* device memory.  Never refracted; mask, vec_tilt and the inner-domain offsets play no part.  HZ_ERR_ARG for num_rays out of   */
+/* range, both or neither of directions and targets, max_dist not finite or <= 0 with directions, order not 0 or 1, no output.  */
+/* stats->num_rays = the rays traced (num_rays minus the targets on their origin).  The rays go in chunks (a multiple of 64):   */
+/* host inputs and host outputs are staged on the device one chunk at a time and order 1 sorts one chunk at a time, together    */
+/* at most 256 MiB ("cast_budget" of hz_debug_set) or 64 rays' worth, plus the sort's histograms (about 2 bytes per ray of a  */
+/* chunk).  hz_stats.scratch_bytes = that memory; it does not grow with num_rays.                                                */
+/* hz_debug_set: "cast_fast_cap" = n entries of the any-hit kernel's fast stack (0: level stack only; < 0: the                  */
+/* default), "cast_sort_only" = 1: order 1 stops after the sort and writes no output (timing).                                  */
+int hz_terrain_cast(hz_terrain *terrain, const float *origins, const float *directions, const float *targets, int num_rays,
+                    float max_dist, int order, uint8_t *occluded, float *dist, float *point, hz_stats *stats);
 /* additive: 1 = later shadow / sw_dir_cor calls run the counting instantiation and also fill   */
 /* hz_stats.nodes_visited / tris_tested / wave_*_iters (slower; for the roofline's B_trav)      */
 int hz_terrain_count_work(hz_terrain *terrain, int on);
