@@ -4,8 +4,14 @@ The reference checks its arguments in a fixed order and raises fixed exception c
 (horizon.pyx:108-153, :279-312; shadow.pyx:87-133); callers and tests depend on class, message and ORDER, so those are the
 contract.  Here every entry point states its checks as a table of rules -- (exception class, message, predicate that is true
 when the argument is BAD) -- and `run` raises the first rule that fires.  Predicates are callables so that a later rule may
-rely on what an earlier one established (shapes before contents)."""
+rely on what an earlier one established (shapes before contents).
+
+What Terrain's observer and ray calls (viewshed, sight_height, panorama, cast) have in common is stated here once: `is_number`
+and `all_finite` for their predicates, and the makers of the three rules every one of them has -- `some_output_given`,
+`all_contiguous`, `distinct_outputs` -- which a call lists in its table like any other rule, at its place in the order."""
 import numpy as np
+
+from ._lib import ptr
 
 ALGORITHMS = ("discrete_sampling", "binary_search", "guess_constant")
 GEOMETRIES = ("triangle", "quad", "grid")
@@ -43,3 +49,40 @@ def window_inside(offset_0, offset_1, shape, dem_dim_0, dem_dim_1):
 
 def unit_vectors(v, tol=1.0e-5):
     return float(np.abs((v ** 2).sum(axis=2) - 1.0).max()) <= tol
+
+
+def is_number(v):
+    """An int, a float or a NumPy scalar of either kind; a bool is not a number."""
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def all_finite(a):
+    """Whether a NumPy array or a torch tensor has finite entries only (a tensor: a reduction on its device, read back)."""
+    if isinstance(a, np.ndarray):
+        return bool(np.isfinite(a).all())
+    import torch
+    return bool(torch.isfinite(a).all().item())
+
+
+def contiguous(a):
+    return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
+
+
+def quoted_names(outs):
+    """'a', 'b' and 'c' of an outputs table (("a", ...), ("b", ...), ("c", ...))."""
+    names = ["'%s'" % row[0] for row in outs]
+    return ", ".join(names[:-1]) + " and " + names[-1]
+
+
+def some_output_given(outs, given):
+    """`outs`: the call's outputs table, a row per output that starts with its name; `given`: the buffers that are not None."""
+    return (ValueError, "at least one of %s must be given" % quoted_names(outs), lambda: not given)
+
+
+def all_contiguous(arrays):
+    """`arrays`: a callable that gives the list, since an earlier rule may have to hold before it can be formed."""
+    return (ValueError, "not all input arrays are C-contiguous", lambda: not all(contiguous(a) for a in arrays()))
+
+
+def distinct_outputs(outs, given):
+    return (ValueError, "%s must be different arrays" % quoted_names(outs), lambda: len({ptr(buf) for buf in given}) != len(given))

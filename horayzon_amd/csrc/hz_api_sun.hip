@@ -5,7 +5,8 @@
 // Ten calls walk their positions in chunks: terrain_run, hz_terrain_accumulate, hz_terrain_sw_dir_cor_coarse,
 // hz_terrain_viewshed, hz_terrain_sight_height, hz_terrain_panorama, hz_terrain_cast, hz_horizon_terrain_run, hz_horizon_terrain_sw_dir_cor_coarse and hz_horizon_terrain_sun_times.  Each reads as checks, plan,
 // allocations, one chunk loop with the launches, finish; what they share -- device, lock, stream, timers, the scratch tally,
-// staged inputs, staged outputs -- is SunCall and ChunkFeed below.
+// staged inputs, staged outputs -- is SunCall, ChunkFeed (an input that goes up chunk by chunk) and ChunkOut (an output that
+// comes down chunk by chunk) below; the seven Terrain calls also share their end, terrain_finish.
 #include "hz_internal.h"
 #include "hz_horisun_plan.h"
 #include "hz_horisun_coarse_plan.h"
@@ -122,6 +123,26 @@ struct ChunkFeed {
     }
 };
 
+// One output of such a call that goes out chunk by chunk, ChunkFeed's mirror image: `per` elements of T per position in host
+// or device memory, or none (null).  at() gives the device address a chunk is written to: the caller's own memory, or the one
+// chunk of device memory a host output is staged in (SunCall::bind), which out() copies to the host after the chunk's
+// launches (stream order keeps it intact until then, and the next chunk's launches wait for the copy).
+template <typename T>
+struct ChunkOut {
+    T *dst;
+    size_t per;
+    bool on_dev;
+    DevBuf chunk;                             // device memory for one chunk of a host output (SunCall::bind)
+    ChunkOut(T *dst_, size_t per_) : dst(dst_), per(per_), on_dev(dst_ && is_device_ptr(dst_)) {}
+    bool staged() const { return dst && !on_dev; }
+    T *at(size_t s0) const { return staged() ? static_cast<T *>(chunk.p) : dst ? dst + per * s0 : nullptr; }
+    int out(size_t s0, int kc, hipStream_t st) const {
+        if (!staged()) return HZ_OK;
+        HZ_HIP(hipMemcpyAsync(dst + per * s0, chunk.p, (size_t)kc * per * sizeof(T), hipMemcpyDeviceToHost, st));
+        return HZ_OK;
+    }
+};
+
 // The common start and end of such a call.  `scratch` adds up the device memory the call allocates besides the caller's
 // buffers: what the calls that report hz_stats.scratch_bytes report.
 struct SunCall {
@@ -152,6 +173,11 @@ struct SunCall {
         const int rc = o.bind(dst, dst ? n : 0);
         if (!rc && o.owned && counts_as_scratch) scratch += n * sizeof(T);
         return rc;
+    }
+    // an output that goes out in chunks of up to k positions: a host output gets one chunk of device memory, which counts as scratch
+    template <typename T>
+    int bind(ChunkOut<T> &o, int k) {
+        return o.staged() ? alloc(o.chunk, (size_t)k * o.per * sizeof(T)) : HZ_OK;
     }
     // staging memory for k positions of every feed, in the order given -- allocated only if one of them reads host memory
     template <typename... F>
@@ -239,6 +265,32 @@ static void horisun_inputs(const HorizonTerrain *t, Args &a) {
     a.cells = (size_t)t->dim_in_0 * (size_t)t->dim_in_1; a.azim_num = t->azim_num;
     a.fill = t->fill;
     a.refrac_fac = t->refrac_fac;
+}
+
+// The end of every Terrain call: the launches are waited for and the counters read back, the outputs staged whole (`outs`) go
+// to the host, and `stats` gets the times and what every Terrain call reports besides them -- with `report_scratch`, also
+// the call's tally as scratch_bytes.
+template <typename... O>
+static int terrain_finish(const Terrain *t, SunCall &call, hz_stats *stats, bool report_scratch, O &...outs) {
+    unsigned long long cnt[HZ_SHADOW_CNT_N];
+    int rc;
+    if ((rc = call.end())) return rc;
+    HZ_HIP(hipMemcpyAsync(cnt, t->counters, HZ_SHADOW_CNT_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, call.st));
+    HZ_HIP(hipStreamSynchronize(call.st));
+    if ((rc = call.finish(stats, outs...)) || !stats) return rc;
+    stats->num_rays += cnt[HZ_SHADOW_CNT_RAYS];
+    stats->nodes_visited += cnt[HZ_SHADOW_CNT_NODES]; stats->tris_tested += cnt[HZ_SHADOW_CNT_TRIS];
+    stats->wave_node_iters += cnt[HZ_SHADOW_CNT_WAVE_NODE]; stats->wave_leaf_iters += cnt[HZ_SHADOW_CNT_WAVE_LEAF];
+    stats->bvh_height = t->scene->hdr.height; stats->scene_bytes = t->scene->hdr.total_bytes;
+    if (report_scratch) stats->scratch_bytes = call.scratch;
+    return HZ_OK;
+}
+
+// 'max_dist' of the line-of-sight calls (ViewshedArgs, SightArgs): anything but a finite distance above 0 is "no limit"
+template <typename A>
+static void set_max_dist(A &v, float max_dist) {
+    v.has_max = (max_dist > 0.0f && std::isfinite(max_dist)) ? 1 : 0;
+    v.max_dist = v.has_max ? max_dist : 0.0f;
 }
 
 }  // namespace hz
@@ -349,27 +401,10 @@ static ShadowArgs terrain_args(const Terrain *t, int which) {
     return a;
 }
 
-// a Terrain call's timed interval: opened with the kernels' counters zeroed, closed with the counters read back
+// a Terrain call's timed interval: opened with the kernels' counters zeroed, closed by terrain_finish (above) with the counters read back
 static int terrain_begin(const Terrain *t, SunCall &call) {
     HZ_HIP(hipMemsetAsync(t->counters, 0, HZ_SHADOW_CNT_N * sizeof(unsigned long long), call.st));
     return call.begin();
-}
-
-static int terrain_end(const Terrain *t, SunCall &call, unsigned long long cnt[HZ_SHADOW_CNT_N]) {
-    const int rc = call.end();
-    if (rc) return rc;
-    HZ_HIP(hipMemcpyAsync(cnt, t->counters, HZ_SHADOW_CNT_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, call.st));
-    HZ_HIP(hipStreamSynchronize(call.st));
-    return HZ_OK;
-}
-
-// what every Terrain call reports besides its times
-static void terrain_stats(const Terrain *t, const unsigned long long *cnt, hz_stats *stats) {
-    if (!stats) return;
-    stats->num_rays += cnt[HZ_SHADOW_CNT_RAYS];
-    stats->nodes_visited += cnt[HZ_SHADOW_CNT_NODES]; stats->tris_tested += cnt[HZ_SHADOW_CNT_TRIS];
-    stats->wave_node_iters += cnt[HZ_SHADOW_CNT_WAVE_NODE]; stats->wave_leaf_iters += cnt[HZ_SHADOW_CNT_WAVE_LEAF];
-    stats->bvh_height = t->scene->hdr.height; stats->scene_bytes = t->scene->hdr.total_bytes;
 }
 
 // host positions (chunks of k) go up through the handle's own buffer: no allocation per call
@@ -410,11 +445,7 @@ static int terrain_run(Terrain *t, const float *sun_positions, int num_sun, int 
         a.out_f32 = d_f32.dev ? d_f32.dev + nc * (size_t)s0 : nullptr;
         if ((rc = shadow_launch(t->scene, a, call.st))) return rc;
     }
-    unsigned long long cnt[HZ_SHADOW_CNT_N];
-    if ((rc = terrain_end(t, call, cnt))) return rc;
-    if ((rc = call.finish(stats, d_u8, d_f32))) return rc;
-    terrain_stats(t, cnt, stats);
-    return HZ_OK;
+    return terrain_finish(t, call, stats, false, d_u8, d_f32);      // no scratch_bytes: these calls never reported it
 }
 
 int hz_terrain_count_work(hz_terrain *terrain, int on) {
@@ -496,12 +527,7 @@ int hz_terrain_accumulate(hz_terrain *terrain, const float *sun_positions, const
         if ((rc = accum_add_launch(a.out_u8, a.out_f32, nc, a.num_sun, w_dev, acc.sw, acc.lit, call.st))) return rc;
     }
     if ((rc = accum_final_launch(a.mask, nc, t->fill, acc.sw, acc.lit, d_sw.dev, d_lit.dev, call.st))) return rc;
-    unsigned long long cnt[HZ_SHADOW_CNT_N];
-    if ((rc = terrain_end(t, call, cnt))) return rc;
-    if ((rc = call.finish(stats, d_sw, d_lit))) return rc;
-    terrain_stats(t, cnt, stats);
-    if (stats) stats->scratch_bytes = call.scratch;
-    return HZ_OK;
+    return terrain_finish(t, call, stats, true, d_sw, d_lit);
 }
 
 // Terrain.sw_dir_cor_coarse (hz_subgrid.hip: k_coarse_count, k_coarse_reduce).  accumulate's chunks and scratch; instead of
@@ -546,12 +572,7 @@ int hz_terrain_sw_dir_cor_coarse(hz_terrain *terrain, const float *sun_positions
                                        d_lit.dev ? d_lit.dev + ng * (size_t)s0 : nullptr, call.st)))
             return rc;
     }
-    unsigned long long cnt[HZ_SHADOW_CNT_N];
-    if ((rc = terrain_end(t, call, cnt))) return rc;
-    if ((rc = call.finish(stats, d_sw, d_lit))) return rc;
-    terrain_stats(t, cnt, stats);
-    if (stats) stats->scratch_bytes = call.scratch;
-    return HZ_OK;
+    return terrain_finish(t, call, stats, true, d_sw, d_lit);
 }
 
 // Terrain.viewshed (hz_viewshed.hip: k_viewshed_refill; DESIGN.md section 4 clause 18).  Observers go in launches of up to
@@ -582,8 +603,7 @@ int hz_terrain_viewshed(hz_terrain *terrain, const float *observers, int num_obs
     a.refrac_cor = 0; a.refrac_fac = nullptr;     // a line of sight is not bent
     ViewshedArgs v;
     v.target_elev = target_elev; v.facing = facing ? 1 : 0;
-    v.has_max = (max_dist > 0.0f && std::isfinite(max_dist)) ? 1 : 0;
-    v.max_dist = v.has_max ? max_dist : 0.0f;
+    set_max_dist(v, max_dist);
     v.seen_count = d_seen.dev;
     if (d_seen.dev) HZ_HIP(hipMemsetAsync(d_seen.dev, 0, nc * sizeof(int32_t), call.st));
     if (d_cells.dev) HZ_HIP(hipMemsetAsync(d_cells.dev, 0, (size_t)num_obs * sizeof(int64_t), call.st));
@@ -597,12 +617,7 @@ int hz_terrain_viewshed(hz_terrain *terrain, const float *observers, int num_obs
         if ((rc = viewshed_launch(t->scene, a, v, call.st))) return rc;
     }
     if ((rc = viewshed_masked_launch(a.mask, nc, d_seen.dev, call.st))) return rc;
-    unsigned long long cnt[HZ_SHADOW_CNT_N];
-    if ((rc = terrain_end(t, call, cnt))) return rc;
-    if ((rc = call.finish(stats, d_vis, d_seen, d_cells))) return rc;
-    terrain_stats(t, cnt, stats);
-    if (stats) stats->scratch_bytes = call.scratch;
-    return HZ_OK;
+    return terrain_finish(t, call, stats, true, d_vis, d_seen, d_cells);
 }
 
 // the rules of sight_height's table (DESIGN.md section 4 clause 19): the kernel indexes it and does no arithmetic on it
@@ -653,8 +668,7 @@ int hz_terrain_sight_height(hz_terrain *terrain, const float *observers, int num
     ShadowArgs a = terrain_args(t, 1);
     a.refrac_cor = 0; a.refrac_fac = nullptr;     // a line of sight is not bent
     v.num_heights = num_heights;
-    v.has_max = (max_dist > 0.0f && std::isfinite(max_dist)) ? 1 : 0;
-    v.max_dist = v.has_max ? max_dist : 0.0f;
+    set_max_dist(v, max_dist);
     v.lowest = d_lowest.dev;
     if ((rc = sight_lowest_init_launch(nc, d_lowest.dev, call.st))) return rc;
     if (d_cells.dev) HZ_HIP(hipMemsetAsync(d_cells.dev, 0, (size_t)num_obs * sizeof(int64_t), call.st));
@@ -668,12 +682,7 @@ int hz_terrain_sight_height(hz_terrain *terrain, const float *observers, int num
         if ((rc = sight_launch(t->scene, a, v, call.st))) return rc;
     }
     if ((rc = sight_masked_launch(a.mask, nc, d_lowest.dev, call.st))) return rc;
-    unsigned long long cnt[HZ_SHADOW_CNT_N];
-    if ((rc = terrain_end(t, call, cnt))) return rc;
-    if ((rc = call.finish(stats, d_height, d_lowest, d_cells))) return rc;
-    terrain_stats(t, cnt, stats);
-    if (stats) stats->scratch_bytes = call.scratch;
-    return HZ_OK;
+    return terrain_finish(t, call, stats, true, d_height, d_lowest, d_cells);
 }
 
 // Terrain.panorama (hz_panorama.hip: k_panorama; DESIGN.md section 4 clause 20).  Observers go in chunks (hz_panorama_plan.h):
@@ -697,15 +706,15 @@ int hz_terrain_panorama(hz_terrain *terrain, const float *observers, int num_obs
     const void *outs[3] = {dist, point, hits};
     int rc;
     if ((rc = check_distinct_outputs(outs, 3))) return rc;
-    const bool stage_dist = dist && !is_device_ptr(dist), stage_point = point && !is_device_ptr(point);
+    const size_t pixels = (size_t)azim_num * (size_t)elev_num;
+    SunCall call;                                 // (before the outputs: their chunks are freed while the call holds its lock)
+    ChunkOut<float> o_dist(dist, pixels), o_point(point, 3 * pixels);
     const int knob = g_panorama_budget.load(std::memory_order_relaxed);       // (hz_debug_set("panorama_budget", bytes): tests)
     PanoramaPlan plan;
-    if (!panorama_plan(num_obs, azim_num, elev_num, stage_dist, stage_point, knob > 0 ? (unsigned long long)knob : HZ_PANORAMA_BUDGET, &plan))
+    if (!panorama_plan(num_obs, azim_num, elev_num, o_dist.staged(), o_point.staged(), knob > 0 ? (unsigned long long)knob : HZ_PANORAMA_BUDGET, &plan))
         return set_error(HZ_ERR_ARG, "panorama: no plan for %d observers of %d x %d pixels", num_obs, elev_num, azim_num);
-    SunCall call;
     if ((rc = call.start(t->device, t->scene->run_mu, t->stream))) return rc;
     const int k = plan.chunk;
-    const size_t pixels = (size_t)plan.pixels;
     ChunkFeed<float> obs(observers, 3), north(vec_north, 3), norm(vec_norm, 3);
     if ((rc = vec_north ? call.stage(k, obs, north, norm) : call.stage(k, obs))) return rc;
     PanoramaArgs a;
@@ -717,12 +726,8 @@ int hz_terrain_panorama(hz_terrain *terrain, const float *observers, int num_obs
                     ((d_es.owned ? 1 : 0) + (d_ec.owned ? 1 : 0)) * (size_t)elev_num * sizeof(float);
     a.azim_sin = d_as.dev; a.azim_cos = d_ac.dev; a.elev_sin = d_es.dev; a.elev_cos = d_ec.dev;
     a.azim_num = azim_num; a.elev_num = elev_num; a.max_dist = max_dist;
-    // a staged output holds one chunk; an output in device memory is the caller's whole array
-    DevOut<float> d_dist, d_point; DevOut<int64_t> d_hits;
-    if ((rc = call.bind(d_dist, dist, stage_dist ? (size_t)k * pixels : (size_t)num_obs * pixels, true)) ||
-        (rc = call.bind(d_point, point, 3 * (stage_point ? (size_t)k * pixels : (size_t)num_obs * pixels), true)) ||
-        (rc = call.bind(d_hits, hits, (size_t)num_obs, false)))
-        return rc;
+    DevOut<int64_t> d_hits;
+    if ((rc = call.bind(o_dist, k)) || (rc = call.bind(o_point, k)) || (rc = call.bind(d_hits, hits, (size_t)num_obs, false))) return rc;
     if (d_hits.dev) HZ_HIP(hipMemsetAsync(d_hits.dev, 0, (size_t)num_obs * sizeof(int64_t), call.st));
     if ((rc = terrain_begin(t, call))) return rc;
     for (int s0 = 0; s0 < num_obs; s0 += k) {
@@ -730,24 +735,14 @@ int hz_terrain_panorama(hz_terrain *terrain, const float *observers, int num_obs
         if ((rc = obs.at(s0, a.num_obs, call.st, &a.observers)) || (rc = north.at(s0, a.num_obs, call.st, &a.vec_north)) ||
             (rc = norm.at(s0, a.num_obs, call.st, &a.vec_norm)))
             return rc;
-        a.dist = d_dist.dev ? d_dist.dev + (stage_dist ? 0 : pixels * (size_t)s0) : nullptr;
-        a.point = d_point.dev ? d_point.dev + (stage_point ? 0 : 3 * pixels * (size_t)s0) : nullptr;
+        a.dist = o_dist.at(s0); a.point = o_point.at(s0);
         a.hits = d_hits.dev ? d_hits.dev + s0 : nullptr;
         if ((rc = panorama_launch(t->scene, a, call.st))) return rc;
         // the chunk's staged images go out before the next chunk is traced into the same memory (stream order)
-        if (stage_dist)
-            HZ_HIP(hipMemcpyAsync(dist + pixels * (size_t)s0, d_dist.dev, (size_t)a.num_obs * pixels * sizeof(float), hipMemcpyDeviceToHost, call.st));
-        if (stage_point)
-            HZ_HIP(hipMemcpyAsync(point + 3 * pixels * (size_t)s0, d_point.dev, 3 * (size_t)a.num_obs * pixels * sizeof(float), hipMemcpyDeviceToHost, call.st));
+        if ((rc = o_dist.out(s0, a.num_obs, call.st)) || (rc = o_point.out(s0, a.num_obs, call.st))) return rc;
     }
-    unsigned long long cnt[HZ_SHADOW_CNT_N];
-    if ((rc = terrain_end(t, call, cnt))) return rc;
-    if ((rc = call.finish(stats, d_hits))) return rc;
-    terrain_stats(t, cnt, stats);
-    if (stats) {
-        stats->num_rays += (unsigned long long)num_obs * plan.pixels;      // every pixel is one ray
-        stats->scratch_bytes = call.scratch;
-    }
+    if ((rc = terrain_finish(t, call, stats, true, d_hits))) return rc;
+    if (stats) stats->num_rays += (unsigned long long)num_obs * plan.pixels;      // every pixel is one ray
     return HZ_OK;
 }
 
@@ -769,24 +764,19 @@ int hz_terrain_cast(hz_terrain *terrain, const float *origins, const float *dire
     int rc;
     if ((rc = check_distinct_outputs(outs, 3))) return rc;
     const float *ends_src = directions ? directions : targets;
-    const bool stage_occ = occluded && !is_device_ptr(occluded), stage_dist = dist && !is_device_ptr(dist),
-               stage_point = point && !is_device_ptr(point);
+    SunCall call;                                 // (before the outputs: their chunks are freed while the call holds its lock)
     ChunkFeed<float> org(origins, 3), ends(ends_src, 3);
+    ChunkOut<uint8_t> o_occ(occluded, 1);
+    ChunkOut<float> o_dist(dist, 1), o_point(point, 3);
     const int knob = g_cast_budget.load(std::memory_order_relaxed);           // (hz_debug_set("cast_budget", bytes): tests)
     CastPlan plan;
-    if (!cast_plan(num_rays, org.staged(), ends.staged(), stage_occ, stage_dist, stage_point, order == 1,
+    if (!cast_plan(num_rays, org.staged(), ends.staged(), o_occ.staged(), o_dist.staged(), o_point.staged(), order == 1,
                    knob > 0 ? (unsigned long long)knob : HZ_CAST_BUDGET, &plan))
         return set_error(HZ_ERR_ARG, "cast: no plan for %d rays", num_rays);
-    SunCall call;
     if ((rc = call.start(t->device, t->scene->run_mu, t->stream))) return rc;
     const int k = plan.chunk;
     if ((rc = org.staged() && ends.staged() ? call.stage(k, org, ends) : org.staged() ? call.stage(k, org) : call.stage(k, ends))) return rc;
-    // a staged output holds one chunk; an output in device memory is the caller's whole array
-    DevOut<uint8_t> d_occ; DevOut<float> d_dist, d_point;
-    if ((rc = call.bind(d_occ, occluded, stage_occ ? (size_t)k : (size_t)num_rays, true)) ||
-        (rc = call.bind(d_dist, dist, stage_dist ? (size_t)k : (size_t)num_rays, true)) ||
-        (rc = call.bind(d_point, point, 3 * (stage_point ? (size_t)k : (size_t)num_rays), true)))
-        return rc;
+    if ((rc = call.bind(o_occ, k)) || (rc = call.bind(o_dist, k)) || (rc = call.bind(o_point, k))) return rc;
     // order = 1: keys and ray numbers, in and out, and the sort's histograms
     DevBuf sort_buf;
     uint32_t *keys_a = nullptr, *vals_a = nullptr, *keys_b = nullptr, *vals_b = nullptr, *sort_tmp = nullptr;
@@ -810,21 +800,12 @@ int hz_terrain_cast(hz_terrain *terrain, const float *origins, const float *dire
             a.perm = vals_a;
         }
         if (!trace) continue;
-        a.occluded = d_occ.dev ? d_occ.dev + (stage_occ ? 0 : (size_t)s0) : nullptr;
-        a.dist = d_dist.dev ? d_dist.dev + (stage_dist ? 0 : (size_t)s0) : nullptr;
-        a.point = d_point.dev ? d_point.dev + (stage_point ? 0 : 3 * (size_t)s0) : nullptr;
+        a.occluded = o_occ.at(s0); a.dist = o_dist.at(s0); a.point = o_point.at(s0);
         if ((rc = cast_launch(t->scene, a, call.st))) return rc;
         // the chunk's staged results go out before the next chunk is traced into the same memory (stream order)
-        if (stage_occ) HZ_HIP(hipMemcpyAsync(occluded + (size_t)s0, d_occ.dev, (size_t)kc, hipMemcpyDeviceToHost, call.st));
-        if (stage_dist) HZ_HIP(hipMemcpyAsync(dist + (size_t)s0, d_dist.dev, (size_t)kc * sizeof(float), hipMemcpyDeviceToHost, call.st));
-        if (stage_point) HZ_HIP(hipMemcpyAsync(point + 3 * (size_t)s0, d_point.dev, 3 * (size_t)kc * sizeof(float), hipMemcpyDeviceToHost, call.st));
+        if ((rc = o_occ.out(s0, kc, call.st)) || (rc = o_dist.out(s0, kc, call.st)) || (rc = o_point.out(s0, kc, call.st))) return rc;
     }
-    unsigned long long cnt[HZ_SHADOW_CNT_N];
-    if ((rc = terrain_end(t, call, cnt))) return rc;
-    if ((rc = call.finish(stats))) return rc;
-    terrain_stats(t, cnt, stats);                   // num_rays: the rays the kernels traced
-    if (stats) stats->scratch_bytes = call.scratch;
-    return HZ_OK;
+    return terrain_finish(t, call, stats, true);    // num_rays: the rays the kernels traced
 }
 
 int hz_terrain_destroy(hz_terrain *terrain) {

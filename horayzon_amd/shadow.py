@@ -13,6 +13,7 @@ import numpy as np
 from . import _lib
 from . import _validate as V
 from ._lib import hz_stats, ptr
+from ._validate import contiguous as _contiguous
 
 
 def _typed(a, dtype, ndim, name):
@@ -24,10 +25,6 @@ def _typed(a, dtype, ndim, name):
     if a.dtype != dtype:
         raise ValueError("Buffer dtype mismatch, expected '%s' but got '%s'"
                          % (np.dtype(dtype).name, a.dtype.name))
-
-
-def _contiguous(a):
-    return a.flags["C_CONTIGUOUS"] if isinstance(a, np.ndarray) else a.is_contiguous()
 
 
 def _accumulate_types(obj, sun_positions, weights, outs):
@@ -164,9 +161,18 @@ class Terrain:
         self._shape = (vec_tilt.shape[0], vec_tilt.shape[1])
         self.last_stats = st.as_dict()
 
-    def _check_out(self, buf, name):
+    def _require_initialised(self):
         if self._shape is None:
             raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
+
+    def _call(self, symbol, *args):
+        """The library's entry point `symbol` on the handle; the hz_stats it fills in become ``last_stats``."""
+        st = hz_stats()
+        _lib.check(getattr(_lib.lib(), symbol)(self._h, *args, C.byref(st)))
+        self.last_stats = st.as_dict()
+
+    def _check_out(self, buf, name):
+        self._require_initialised()
         if tuple(buf.shape[-2:]) != self._shape:
             raise ValueError("array '%s' has incorrect shape" % name)
 
@@ -181,10 +187,7 @@ class Terrain:
         if not shadow_buffer.flags["C_CONTIGUOUS"]:
             raise ValueError("array 'shadow_buffer' is not C-contiguous")
         self._check_out(shadow_buffer, "shadow_buffer")
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_shadow(self._h, ptr(np.ascontiguousarray(sun_position)),
-                                                ptr(shadow_buffer), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_terrain_shadow", ptr(np.ascontiguousarray(sun_position)), ptr(shadow_buffer))
 
     def sw_dir_cor(self, sun_position, sw_dir_cor_buffer):
         """Compute shortwave correction factor for specified sun position."""
@@ -196,10 +199,7 @@ class Terrain:
         if not sw_dir_cor_buffer.flags["C_CONTIGUOUS"]:
             raise ValueError("array 'sw_dir_cor_buffer' is not C-contiguous")
         self._check_out(sw_dir_cor_buffer, "sw_dir_cor_buffer")
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_sw_dir_cor(self._h, ptr(np.ascontiguousarray(sun_position)),
-                                                    ptr(sw_dir_cor_buffer), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_terrain_sw_dir_cor", ptr(np.ascontiguousarray(sun_position)), ptr(sw_dir_cor_buffer))
 
     def count_work(self, on=True):
         """Additive: later calls also count BVH node visits / triangle tests (``last_stats``; slower)."""
@@ -232,11 +232,8 @@ class Terrain:
         if sun_positions.shape[1] != 3 or shadow_buffers.shape[0] != sun_positions.shape[0]:
             raise ValueError("array 'sun_positions' has incorrect shape")
         self._check_out(shadow_buffers, "shadow_buffers")
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_shadow_batch(
-            self._h, ptr(np.ascontiguousarray(sun_positions)), sun_positions.shape[0],
-            ptr(shadow_buffers), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_terrain_shadow_batch", ptr(np.ascontiguousarray(sun_positions)), sun_positions.shape[0],
+                   ptr(shadow_buffers))
 
     def sw_dir_cor_batch(self, sun_positions, sw_dir_cor_buffers):
         """``sw_dir_cor`` for sun_positions f32[num][3] -> sw_dir_cor_buffers f32[num][y][x] (NumPy or torch/HBM)."""
@@ -245,11 +242,8 @@ class Terrain:
         if sun_positions.shape[1] != 3 or sw_dir_cor_buffers.shape[0] != sun_positions.shape[0]:
             raise ValueError("array 'sun_positions' has incorrect shape")
         self._check_out(sw_dir_cor_buffers, "sw_dir_cor_buffers")
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_sw_dir_cor_batch(
-            self._h, ptr(np.ascontiguousarray(sun_positions)), sun_positions.shape[0],
-            ptr(sw_dir_cor_buffers), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_terrain_sw_dir_cor_batch", ptr(np.ascontiguousarray(sun_positions)), sun_positions.shape[0],
+                   ptr(sw_dir_cor_buffers))
 
     # --- additive: weighted sums over many sun positions, no map per position -------------------------------------
     def _array_arg(self, buf, ndim, name, np_dtype=np.float32, owner="Terrain"):
@@ -267,6 +261,13 @@ class Terrain:
         if buf.device.type != "cuda" or buf.device.index != self.device:
             raise ValueError("tensor '%s' is not on the %s's device (cuda:%d)" % (name, owner, self.device))
 
+    def _given_outputs(self, outs):
+        """The outputs that were given, out of the table ((name, buf, ndim, dtype), ...), after their types are checked."""
+        for name, buf, ndim, dtype in outs:
+            if buf is not None:
+                self._array_arg(buf, ndim, name, dtype)
+        return [buf for _, buf, _, _ in outs if buf is not None]
+
     def accumulate(self, sun_positions, weights=None, *, sw_dir_cor_sum=None, sunlit_sum=None):
         """Weighted sums over sun_positions f32[S][3] (S >= 1) without a map per position:
         ``sw_dir_cor_sum`` = sum of weights[s] * sw_dir_cor(sun_positions[s]) and ``sunlit_sum`` = sum of weights[s] over
@@ -280,11 +281,8 @@ class Terrain:
         for name, buf in outs:
             if buf is not None:
                 self._check_out(buf, name)
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_accumulate(
-            self._h, ptr(sun_positions), ptr(weights), sun_positions.shape[0],
-            ptr(sw_dir_cor_sum), ptr(sunlit_sum), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_terrain_accumulate", ptr(sun_positions), ptr(weights), sun_positions.shape[0],
+                   ptr(sw_dir_cor_sum), ptr(sunlit_sum))
 
     # --- additive: block means per sun position (sub-grid look-up tables), no map per position ---------------------
     @staticmethod
@@ -330,49 +328,32 @@ class Terrain:
         outs = (("visible", visible, 3, np.uint8), ("seen_count", seen_count, 2, np.int32),
                 ("cells_seen", cells_seen, 1, np.int64))
         self._array_arg(observers, 2, "observers")
-        for name, buf, ndim, dtype in outs:
-            if buf is not None:
-                self._array_arg(buf, ndim, name, dtype)
-
-        def number(v):
-            return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-        if not number(target_elev):
+        given = self._given_outputs(outs)
+        if not V.is_number(target_elev):
             raise TypeError("Argument 'target_elev' has incorrect type (expected a number, got %s)" % type(target_elev).__name__)
-        if max_dist is not None and not number(max_dist):
+        if max_dist is not None and not V.is_number(max_dist):
             raise TypeError("Argument 'max_dist' has incorrect type (expected a number or None, got %s)" % type(max_dist).__name__)
         if not isinstance(facing, (bool, np.bool_)):
             raise TypeError("Argument 'facing' has incorrect type (expected bool, got %s)" % type(facing).__name__)
-        given = [buf for _, buf, _, _ in outs if buf is not None]
-
-        def finite():
-            if _is_tensor(observers):
-                import torch
-                return bool(torch.isfinite(observers).all().item())
-            return bool(np.isfinite(observers).all())
         V.run((
-            (ValueError, "at least one of 'visible', 'seen_count' and 'cells_seen' must be given", lambda: not given),
+            V.some_output_given(outs, given),
             (ValueError, "array 'observers' has incorrect shape", lambda: observers.shape[1] != 3 or observers.shape[0] < 1),
             (ValueError, "array 'visible' has incorrect shape",
              lambda: visible is not None and visible.shape[0] != observers.shape[0]),
             (ValueError, "array 'cells_seen' has incorrect shape",
              lambda: cells_seen is not None and cells_seen.shape[0] != observers.shape[0]),
-            (ValueError, "not all input arrays are C-contiguous", lambda: not all(_contiguous(a) for a in [observers] + given)),
-            (ValueError, "'visible', 'seen_count' and 'cells_seen' must be different arrays",
-             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            V.all_contiguous(lambda: [observers] + given),
+            V.distinct_outputs(outs, given),
             (ValueError, "'target_elev' must be at least 0.005 m", lambda: not (np.isfinite(target_elev) and target_elev >= 0.005)),
             (ValueError, "'max_dist' must be None or greater than 0", lambda: max_dist is not None and not np.float32(max_dist) > 0),
-            (ValueError, "array 'observers' has non-finite entries", lambda: not finite()),
+            (ValueError, "array 'observers' has non-finite entries", lambda: not V.all_finite(observers)),
         ))
         for name, buf in (("visible", visible), ("seen_count", seen_count)):
             if buf is not None:
                 self._check_out(buf, name)
-        if self._shape is None:
-            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_viewshed(
-            self._h, ptr(observers), observers.shape[0], float(target_elev), 0.0 if max_dist is None else float(max_dist),
-            int(bool(facing)), ptr(visible), ptr(seen_count), ptr(cells_seen), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._require_initialised()
+        self._call("hz_terrain_viewshed", ptr(observers), observers.shape[0], float(target_elev),
+                   0.0 if max_dist is None else float(max_dist), int(bool(facing)), ptr(visible), ptr(seen_count), ptr(cells_seen))
 
     # --- additive: depth images of the terrain from observer points -----------------------------------------------------
     def panorama(self, observers, azim, elev, max_dist, *, dist=None, point=None, hits=None,
@@ -396,21 +377,12 @@ class Terrain:
         self._array_arg(observers, 2, "observers")
         for name, tab in (("azim", azim), ("elev", elev)):
             _typed(tab, np.float32, 1, name)
-        if not isinstance(max_dist, (int, float, np.integer, np.floating)) or isinstance(max_dist, (bool, np.bool_)):
+        if not V.is_number(max_dist):
             raise TypeError("Argument 'max_dist' has incorrect type (expected a number, got %s)" % type(max_dist).__name__)
-        for name, buf, ndim, dtype in outs:
-            if buf is not None:
-                self._array_arg(buf, ndim, name, dtype)
+        given = self._given_outputs(outs)
         frames = [(name, v) for name, v in (("vec_north", vec_north), ("vec_norm", vec_norm)) if v is not None]
         for name, v in frames:
             _typed(v, np.float32, 2, name)
-        given = [buf for _, buf, _, _ in outs if buf is not None]
-
-        def finite():
-            if _is_tensor(observers):
-                import torch
-                return bool(torch.isfinite(observers).all().item())
-            return bool(np.isfinite(observers).all())
 
         def image_shape():
             return (observers.shape[0], elev.shape[0], azim.shape[0])
@@ -418,7 +390,7 @@ class Terrain:
         with np.errstate(over="ignore"):
             tfar = np.float32(max_dist)                      # the ray length the kernel sees
         V.run((
-            (ValueError, "at least one of 'dist', 'point' and 'hits' must be given", lambda: not given),
+            V.some_output_given(outs, given),
             (ValueError, "array 'observers' has incorrect shape", lambda: observers.shape[1] != 3 or observers.shape[0] < 1),
             (ValueError, "array 'azim' must have at least one entry", lambda: azim.shape[0] < 1),
             (ValueError, "array 'elev' must have at least one entry", lambda: elev.shape[0] < 1),
@@ -431,29 +403,23 @@ class Terrain:
             (ValueError, "'vec_north' and 'vec_norm' must be given together", lambda: len(frames) == 1),
             (ValueError, "Inconsistent/incorrect shape of 'vec_north' and/or 'vec_norm'",
              lambda: any(tuple(v.shape) != (observers.shape[0], 3) for _, v in frames)),
-            (ValueError, "not all input arrays are C-contiguous",
-             lambda: not all(_contiguous(a) for a in [observers, azim, elev] + [v for _, v in frames] + given)),
-            (ValueError, "'dist', 'point' and 'hits' must be different arrays",
-             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            V.all_contiguous(lambda: [observers, azim, elev] + [v for _, v in frames] + given),
+            V.distinct_outputs(outs, given),
             (ValueError, "'max_dist' must be finite and greater than 0", lambda: not (np.isfinite(tfar) and tfar > 0)),
             (ValueError, "array 'azim' has non-finite entries", lambda: not np.isfinite(azim).all()),
             (ValueError, "array 'elev' has non-finite entries", lambda: not np.isfinite(elev).all()),
             (ValueError, "'elev' must lie in [-pi/2, pi/2]", lambda: bool((elev < -half_pi).any() or (elev > half_pi).any())),
             (ValueError, "Vectors in 'vec_north' and/or 'vec_norm' are not normalised",
              lambda: not all(V.unit_vectors(v[None]) for _, v in frames)),
-            (ValueError, "array 'observers' has non-finite entries", lambda: not finite()),
+            (ValueError, "array 'observers' has non-finite entries", lambda: not V.all_finite(observers)),
         ))
-        if self._shape is None:
-            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
+        self._require_initialised()
         # the four tables of the clause: float64 sin / cos, rounded to float32 once
         azim_sin, azim_cos = np.sin(azim.astype(np.float64)).astype(np.float32), np.cos(azim.astype(np.float64)).astype(np.float32)
         elev_sin, elev_cos = np.sin(elev.astype(np.float64)).astype(np.float32), np.cos(elev.astype(np.float64)).astype(np.float32)
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_panorama(
-            self._h, ptr(observers), observers.shape[0], ptr(azim_sin), ptr(azim_cos), azim.shape[0],
-            ptr(elev_sin), ptr(elev_cos), elev.shape[0], ptr(vec_north), ptr(vec_norm), float(tfar),
-            ptr(dist), ptr(point), ptr(hits), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_terrain_panorama", ptr(observers), observers.shape[0], ptr(azim_sin), ptr(azim_cos), azim.shape[0],
+                   ptr(elev_sin), ptr(elev_cos), elev.shape[0], ptr(vec_north), ptr(vec_norm), float(tfar),
+                   ptr(dist), ptr(point), ptr(hits))
 
     # --- additive: any-hit and closest-hit for the caller's own rays ----------------------------------------------------
     def cast(self, origins, directions=None, *, targets=None, max_dist=None, occluded=None, dist=None, point=None,
@@ -488,19 +454,9 @@ class Terrain:
         self._array_arg(origins, 2, "origins")
         for name, v in ends:
             self._array_arg(v, 2, name)
-        if max_dist is not None and (not isinstance(max_dist, (int, float, np.integer, np.floating)) or
-                                     isinstance(max_dist, (bool, np.bool_))):
+        if max_dist is not None and not V.is_number(max_dist):
             raise TypeError("Argument 'max_dist' has incorrect type (expected a number, got %s)" % type(max_dist).__name__)
-        for name, buf, ndim, dtype in outs:
-            if buf is not None:
-                self._array_arg(buf, ndim, name, dtype)
-        given = [buf for _, buf, _, _ in outs if buf is not None]
-
-        def finite(a):
-            if _is_tensor(a):
-                import torch
-                return bool(torch.isfinite(a).all().item())
-            return bool(np.isfinite(a).all())
+        given = self._given_outputs(outs)
 
         def unit(v):
             if _is_tensor(v):
@@ -513,7 +469,7 @@ class Terrain:
             (ValueError, "exactly one of 'directions' and 'targets' must be given", lambda: len(ends) != 1),
             (ValueError, "'max_dist' must be given with 'directions'", lambda: directions is not None and max_dist is None),
             (ValueError, "'max_dist' must be None with 'targets'", lambda: targets is not None and max_dist is not None),
-            (ValueError, "at least one of 'occluded', 'dist' and 'point' must be given", lambda: not given),
+            V.some_output_given(outs, given),
             (ValueError, "'order' must be 'given' or 'sorted'", lambda: not isinstance(order, str) or order not in ("given", "sorted")),
             (ValueError, "array 'origins' has incorrect shape", lambda: origins.shape[1] != 3 or n() < 1),
             (ValueError, "'origins' must not have more than 2**31 - 64 rays", lambda: n() > 2 ** 31 - 64),
@@ -522,23 +478,17 @@ class Terrain:
             (ValueError, "array 'occluded' has incorrect shape", lambda: occluded is not None and tuple(occluded.shape) != (n(),)),
             (ValueError, "array 'dist' has incorrect shape", lambda: dist is not None and tuple(dist.shape) != (n(),)),
             (ValueError, "array 'point' has incorrect shape", lambda: point is not None and tuple(point.shape) != (n(), 3)),
-            (ValueError, "not all input arrays are C-contiguous",
-             lambda: not all(_contiguous(a) for a in [origins, ends[0][1]] + given)),
-            (ValueError, "'occluded', 'dist' and 'point' must be different arrays",
-             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            V.all_contiguous(lambda: [origins, ends[0][1]] + given),
+            V.distinct_outputs(outs, given),
             (ValueError, "'max_dist' must be finite and greater than 0",
              lambda: directions is not None and not (np.isfinite(tfar) and tfar > 0)),
-            (ValueError, "array 'origins' has non-finite entries", lambda: not finite(origins)),
-            (ValueError, "array '%s' has non-finite entries" % ends[0][0] if ends else "", lambda: not finite(ends[0][1])),
+            (ValueError, "array 'origins' has non-finite entries", lambda: not V.all_finite(origins)),
+            (ValueError, "array '%s' has non-finite entries" % ends[0][0] if ends else "", lambda: not V.all_finite(ends[0][1])),
             (ValueError, "Vectors in 'directions' are not normalised", lambda: directions is not None and not unit(directions)),
         ))
-        if self._shape is None:
-            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_cast(
-            self._h, ptr(origins), ptr(directions), ptr(targets), origins.shape[0], float(tfar),
-            1 if order == "sorted" else 0, ptr(occluded), ptr(dist), ptr(point), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._require_initialised()
+        self._call("hz_terrain_cast", ptr(origins), ptr(directions), ptr(targets), origins.shape[0], float(tfar),
+                   1 if order == "sorted" else 0, ptr(occluded), ptr(dist), ptr(point))
 
     # --- additive: the lowest target height in sight, per observer and cell --------------------------------------------
     def sight_height(self, observers, heights, *, height=None, lowest=None, cells_reached=None, max_dist=None):
@@ -560,47 +510,31 @@ class Terrain:
         if not isinstance(heights, np.ndarray):
             raise TypeError("Argument 'heights' has incorrect type (expected numpy.ndarray, got %s)" % type(heights).__name__)
         _typed(heights, np.float32, 1, "heights")
-        for name, buf, ndim, dtype in outs:
-            if buf is not None:
-                self._array_arg(buf, ndim, name, dtype)
-        if max_dist is not None and (not isinstance(max_dist, (int, float, np.integer, np.floating)) or
-                                     isinstance(max_dist, (bool, np.bool_))):
+        given = self._given_outputs(outs)
+        if max_dist is not None and not V.is_number(max_dist):
             raise TypeError("Argument 'max_dist' has incorrect type (expected a number or None, got %s)" % type(max_dist).__name__)
-        given = [buf for _, buf, _, _ in outs if buf is not None]
-
-        def finite():
-            if _is_tensor(observers):
-                import torch
-                return bool(torch.isfinite(observers).all().item())
-            return bool(np.isfinite(observers).all())
         V.run((
-            (ValueError, "at least one of 'height', 'lowest' and 'cells_reached' must be given", lambda: not given),
+            V.some_output_given(outs, given),
             (ValueError, "array 'observers' has incorrect shape", lambda: observers.shape[1] != 3 or observers.shape[0] < 1),
             (ValueError, "array 'heights' must have 1 to 65535 entries", lambda: not 1 <= heights.shape[0] <= 65535),
             (ValueError, "array 'height' has incorrect shape",
              lambda: height is not None and height.shape[0] != observers.shape[0]),
             (ValueError, "array 'cells_reached' has incorrect shape",
              lambda: cells_reached is not None and cells_reached.shape[0] != observers.shape[0]),
-            (ValueError, "not all input arrays are C-contiguous",
-             lambda: not all(_contiguous(a) for a in [observers, heights] + given)),
-            (ValueError, "'height', 'lowest' and 'cells_reached' must be different arrays",
-             lambda: len({ptr(buf) for buf in given}) != len(given)),
+            V.all_contiguous(lambda: [observers, heights] + given),
+            V.distinct_outputs(outs, given),
             (ValueError, "array 'heights' has non-finite entries", lambda: not np.isfinite(heights).all()),
             (ValueError, "'heights' must start at 0.005 m or above", lambda: not heights[0] >= np.float32(0.005)),
             (ValueError, "'heights' must be strictly increasing", lambda: not (heights[1:] > heights[:-1]).all()),
             (ValueError, "'max_dist' must be None or greater than 0", lambda: max_dist is not None and not np.float32(max_dist) > 0),
-            (ValueError, "array 'observers' has non-finite entries", lambda: not finite()),
+            (ValueError, "array 'observers' has non-finite entries", lambda: not V.all_finite(observers)),
         ))
         for name, buf in (("height", height), ("lowest", lowest)):
             if buf is not None:
                 self._check_out(buf, name)
-        if self._shape is None:
-            raise _lib.HorayzonHipError("%s is not initialised" % self._NAME)
-        st = hz_stats()
-        _lib.check(_lib.lib().hz_terrain_sight_height(
-            self._h, ptr(observers), observers.shape[0], ptr(heights), heights.shape[0],
-            0.0 if max_dist is None else float(max_dist), ptr(height), ptr(lowest), ptr(cells_reached), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._require_initialised()
+        self._call("hz_terrain_sight_height", ptr(observers), observers.shape[0], ptr(heights), heights.shape[0],
+                   0.0 if max_dist is None else float(max_dist), ptr(height), ptr(lowest), ptr(cells_reached))
 
 
 def sight_heights(height_max, height_acc=0.25, height_min=0.05):
@@ -609,7 +543,7 @@ def sight_heights(height_max, height_acc=0.25, height_min=0.05):
     than one step).  ValueError if the table would have more than 65535 entries, if it would start below 0.005 m, or if
     rounding to float32 makes two neighbours equal (a step too fine for the heights)."""
     for name, v in (("height_max", height_max), ("height_acc", height_acc), ("height_min", height_min)):
-        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, (bool, np.bool_)):
+        if not V.is_number(v):
             raise TypeError("Argument '%s' has incorrect type (expected a number, got %s)" % (name, type(v).__name__))
     lo, hi, acc = np.float64(height_min), np.float64(height_max), np.float64(height_acc)
     if not (np.isfinite(lo) and np.isfinite(hi) and np.isfinite(acc)):
@@ -794,8 +728,7 @@ class HorizonTerrain:
         ``initialise_azim_major`` and ``initialise_q16`` switch it off again."""
         if elevation is not None:
             _typed(elevation, np.float32, 2, "elevation")
-        if self._shape is None:
-            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
+        self._require_initialised()
         if elevation is not None:
             if tuple(elevation.shape) != self._shape:
                 raise ValueError("array 'elevation' has incorrect shape")
@@ -815,14 +748,13 @@ class HorizonTerrain:
     _batch_out = staticmethod(Terrain._batch_out)
     _array_arg = Terrain._array_arg
 
+    _require_initialised = Terrain._require_initialised
+    _call = Terrain._call
     _check_out = Terrain._check_out
 
     def _run(self, sun_positions, weights, num_sun, **outs):
-        st = hz_stats()
         out = _lib.hz_horisun_out(**{k: ptr(v) for k, v in outs.items()})
-        _lib.check(_lib.lib().hz_horizon_terrain_run(self._h, ptr(sun_positions), ptr(weights), num_sun,
-                                                     C.byref(out), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_horizon_terrain_run", ptr(sun_positions), ptr(weights), num_sun, C.byref(out))
 
     def shadow(self, sun_position, shadow_buffer):
         """Compute shadow mask for specified sun position
@@ -926,8 +858,7 @@ class HorizonTerrain:
         for name, buf, dtype in outs:
             if buf is not None:
                 self._array_arg(buf, 2, name, dtype, self._NAME)
-        if self._shape is None:
-            raise _lib.HorayzonHipError("HorizonTerrain is not initialised")
+        self._require_initialised()
         given = [(name, buf) for name, buf, _ in outs if buf is not None]
         V.run((
             (ValueError, "at least one of 'sunrise', 'sunset', 'duration' and 'intervals' must be given", lambda: not given),
@@ -945,8 +876,5 @@ class HorizonTerrain:
             (ValueError, "'times' must be finite and strictly increasing",
              lambda: not (np.isfinite(times).all() and (np.diff(times) > 0.0).all())),
         ))
-        st = hz_stats()
         out = _lib.hz_suntimes_out(**{name: ptr(buf) for name, buf in given})
-        _lib.check(_lib.lib().hz_horizon_terrain_sun_times(self._h, ptr(sun_positions), ptr(times), sun_positions.shape[0],
-                                                           C.byref(out), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call("hz_horizon_terrain_sun_times", ptr(sun_positions), ptr(times), sun_positions.shape[0], C.byref(out))

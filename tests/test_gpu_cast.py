@@ -252,6 +252,23 @@ def test_tensors_in_and_out_equal_the_numpy_call(small, mode):
     check((None, d_dist.cpu().numpy(), None, dict(t.last_stats)), ref)
 
 
+def test_staged_and_device_outputs_in_one_chunked_call(small):
+    """Chunks of 1024 rays and a last one of 3, with `occluded` and `point` staged anew for every chunk and `dist` a tensor
+    written in place at the chunk's offset."""
+    torch = pytest.importorskip("torch")
+    t = small.t
+    org, ends = small.sets["targets"]
+    dev = "cuda:%d" % t.device
+    occ, _, point = buffers(N, (True, False, True))
+    d_dist = torch.full((N,), float(JUNK), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    with knob("cast_budget", 25 * 1024 + 24):               # staged per ray: 12 of origins, 1 of occluded, 12 of point
+        t.cast(org, targets=torch.from_numpy(ends).to(dev), occluded=occ, dist=d_dist, point=point)
+    torch.cuda.synchronize()
+    check((occ, d_dist.cpu().numpy(), point, dict(t.last_stats)), small.ref("targets"))
+    assert t.last_stats["scratch_bytes"] == 1024 * 25
+
+
 def test_panoramas_rays_give_the_panoramas_words(small):
     """cast(directions = the panorama's rays) is Terrain.panorama's dist and point, the observer on a vertex included."""
     t, g = small.t, small.g

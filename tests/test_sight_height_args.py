@@ -9,33 +9,11 @@ import pytest
 
 from horayzon_amd import _lib
 from horayzon_amd.shadow import Terrain, sight_heights
+from tests.terrain_args import _terrain, no_library  # noqa: F401 -- pytest finds the fixture in this namespace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE = (6, 7)
 S = 5
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    """Replaces the library loader: any call that reaches it fails the test (the checks must come first)."""
-    calls = []
-
-    def forbidden():
-        calls.append(1)
-        raise AssertionError("the library was called although the arguments are invalid")
-    monkeypatch.setattr(_lib, "lib", forbidden)
-    yield calls
-    assert calls == []
-
-
-def _terrain(shape=SHAPE):
-    """A Terrain that looks initialised to the Python checks, without a device behind it."""
-    t = Terrain.__new__(Terrain)
-    t._h = None
-    t._shape = shape
-    t.device = 0
-    t.last_stats = None
-    return t
 
 
 def _obs(n=S):
